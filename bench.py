@@ -17,7 +17,14 @@ rank.  Every rank solves its own 2048^2 image (independent problems, no data-pat
 ranks' images form one batch-as-axis problem for the GLOBAL RelError: one RCCL all-reduce of 2
 doubles per stop check) -> weak scaling; value = total image-iterations/s = ranks * K / max_rank(t).
 
-Sub-records on the same line (north_star):
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, primes, warms up, times the K steps and prints the
+result line: nothing else.  `--dump-outputs DIR` also writes what the last timed step returned (the item of
+Solver.steps(): the iterate x) as DIR/x.npy (x_rank<r>.npy per rank at N > 1), float32, copied out right after
+the timed region; the inputs are seeded, so the same arguments give the same problem in every run.  Everything
+below -- the kernel-time window and `roofline`, `cpu_baseline`, the sub-records -- is measured only under
+`--full` (`--only NAME` runs one sub-record by itself, with or without it).
+
+Sub-records on the same line under --full (north_star):
   "stop_rate_1": the headline workload at the reference's default stop_rate = 1 (--sr1-steps, default 200 timed steps);
   "c2_4096": the same PGD at 4096^2 (SURVEY §7's stand-in for the infeasible 4096^3 north_star volume);
   "c5": configs[4], 512 independent 512^2 TV-deblur images as ONE (512, 512, 512) batch-as-axis
@@ -443,9 +450,10 @@ def prime_loop(ctx, gen, seconds, chunk=200, sync=None):
     return n
 
 
-def timed_steps(ctx, gen, warmup, steps, timer=None):
+def timed_steps(ctx, gen, warmup, steps, timer=None, keep=None):
     """W untimed steps, then exactly `steps` steps bracketed by barrier + synchronize on both sides;
-    returns the max-over-ranks elapsed seconds."""
+    returns the max-over-ranks elapsed seconds.  `keep` (a list) receives the item steps() yielded for the
+    last timed step: what a caller of the timed path holds when the region ends."""
     import torch
 
     from pyxu_amd import _dev
@@ -456,20 +464,49 @@ def timed_steps(ctx, gen, warmup, steps, timer=None):
     ctx.barrier()
     if timer is not None:
         _dev.set_launch_timer(timer)
+    item = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        next(gen)
+        item = next(gen)
     if timer is not None:
         timer.close()  # close the last window right behind the last launch (before the host sync)
     torch.cuda.synchronize()
     ctx.barrier()
     elapsed = time.perf_counter() - t0
     _dev.set_launch_timer(None)
+    if keep is not None:
+        keep.append(item)
     return ctx.max_over_ranks(elapsed)
 
 
-def run_pgd(ctx, f, g, stop_rate, warmup, steps, fused, prime_s=0.0, kernel_timer=True):
-    """Build a PGD solver in MANUAL mode on (f, g), prime the device, time `steps` steps."""
+DUMP_MAX_BYTES = 60 * 10**6  # --dump-outputs: array data of all files together (under 64 MB with the headers)
+
+
+def sample_output(a, max_bytes, seed=0):
+    """`a` as a flat float32 / float64 array of at most `max_bytes`: whole when it fits, else the elements at a
+    fixed, seeded, sorted set of indices (the same indices for the same size and seed in every run)."""
+    a = np.ascontiguousarray(a).reshape(-1)
+    if a.dtype not in (np.float32, np.float64):
+        a = a.astype(np.float64)
+    cap = max_bytes // a.itemsize
+    if a.size <= cap:
+        return a
+    idx = np.sort(np.random.default_rng(seed).choice(a.size, size=cap, replace=False))
+    return a[idx]
+
+
+def dump_outputs(path, arrays, max_bytes=DUMP_MAX_BYTES):
+    """Write {name: array} as path/<name>.npy, `max_bytes` in all (each array an equal share, sampled by
+    sample_output when larger)."""
+    os.makedirs(path, exist_ok=True)
+    share = max_bytes // max(1, len(arrays))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), sample_output(a, share))
+
+
+def run_pgd(ctx, f, g, stop_rate, warmup, steps, fused, prime_s=0.0, kernel_timer=True, outputs=None):
+    """Build a PGD solver in MANUAL mode on (f, g), prime the device, time `steps` steps.  `outputs` (a dict)
+    receives the host copy of every array of the last timed step's item (PGD: the iterate x)."""
     import torch
 
     import pyxu_amd.abc as pxa
@@ -502,7 +539,12 @@ def run_pgd(ctx, f, g, stop_rate, warmup, steps, fused, prime_s=0.0, kernel_time
     fused_on = slvr._plan is not None
     gen = slvr.steps()
     timer = _dev.LaunchTimer(single=True) if (kernel_timer == "in_region" and fused_on) else None
-    elapsed = timed_steps(ctx, gen, warmup, steps, timer)
+    keep = [] if outputs is not None else None
+    elapsed = timed_steps(ctx, gen, warmup, steps, timer, keep)
+    if keep and keep[0] is not None:  # copied out before anything else steps the solver
+        from pyxu_amd.util import to_NUMPY
+
+        outputs.update({k: to_NUMPY(v) for k, v in keep[0].items() if v is not None})
     if kernel_timer is True and fused_on:
         # the kernel's average launch duration, HIP events on its own stream over a window of `steps` more
         # launches of the same solver right after the timed region: a timing event anywhere in a window makes
@@ -948,20 +990,25 @@ def sub_cpu_baselines(sub, args):
 
 
 # ----------------------------------------------------------------------------- main
-def main():
+def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: the kernel-time window and roofline, the CPU baselines "
+                         "and the stop_rate_1 / c2_4096 / c5 / c4 / c3 / k4 / dense_mfma sub-records")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the PGD iterate x) as DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=2048, help="image side (configs[1]: 2048)")
     ap.add_argument("--stop-rate", type=int, default=0, help="stop-criterion rate (0: largest divisor of --steps <= 50)")
     ap.add_argument("--prime-seconds", type=float, default=0.4, help="untimed device priming before the warmup")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU-baseline time budget per leg in s (0 = skip)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU-baseline time budget per leg in s (0 = skip)")
     ap.add_argument("--generic", action="store_true", help="disable the fused m_step (rule-by-rule HIP path)")
-    ap.add_argument("--no-kernel-timer", action="store_true", help="skip the HIP-event kernel timing window (A/B)")
+    ap.add_argument("--no-kernel-timer", action="store_true", help="--full: skip the HIP-event kernel timing window (A/B)")
     ap.add_argument("--kernel-timer-in-region", action="store_true",
                     help="time the kernel with HIP events inside the timed region (they slow its launches)")
-    ap.add_argument("--no-sub", action="store_true", help="headline line only (no stop_rate_1 / c5 / c4 records)")
+    ap.add_argument("--no-sub", action="store_true", help="--full: no sub-records (stop_rate_1 / c5 / c4 ...)")
     ap.add_argument("--only", default="", help="run only this sub-record (c2_4096 | c5 | c4 | c3) and print it (profiling)")
     ap.add_argument("--sr1-steps", type=int, default=200, help="stop_rate_1 record: timed steps (at least --steps)")
     ap.add_argument("--sr1-warmup", type=int, default=20, help="stop_rate_1 record: warmup steps (at least --warmup)")
@@ -985,10 +1032,11 @@ def main():
     ap.add_argument("--k4-which", default="2d,3d", help="k4 record: shapes to time (2d = 2048^2, 3d = c3-n^3)")
     ap.add_argument("--sub-cpu-seconds", type=float, default=5.0,
                     help="CPU-baseline budget of the c2_4096 / c5 / c4 sub-records in s (0 = skip)")
-    args = ap.parse_args()
+    argv = sys.argv[1:] if argv is None else list(argv)
+    args = ap.parse_args(argv)
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        sys.exit(launch(sys.argv[1:], args.gpus))
+        sys.exit(launch(argv, args.gpus))
 
     import torch
     import torch.distributed as dist
@@ -1032,18 +1080,25 @@ def main():
     N = n0 * n1
     sr = args.stop_rate or auto_stop_rate(args.steps)
     f, g, _ = build_problem(n0, n1, seed=1234 + rank)
+    outputs = {} if args.dump_outputs else None
     with pxrt.Precision(pxrt.Width.SINGLE):
+        # the kernel-time window is K more launches after the timed region: a --full figure
         elapsed_max, kern_ms, slvr, launches = run_pgd(ctx, f, g, sr, args.warmup, args.steps, not args.generic,
                                                        prime_s=args.prime_seconds,
                                                        kernel_timer=("in_region" if args.kernel_timer_in_region else
-                                                                     not args.no_kernel_timer))
+                                                                     args.full and not args.no_kernel_timer),
+                                                       outputs=outputs)
     fused = slvr._plan is not None
     stack = slvr._plan["stack"] if fused else 1
     mode, bpp = last_pgd_mode()
     del slvr
+    if outputs is not None:  # every rank's own image: <name>.npy on one GPU, <name>_rank<r>.npy on several
+        tag = f"_rank{rank}" if world > 1 else ""
+        dump_outputs(args.dump_outputs, {k + tag: v for k, v in outputs.items()}, DUMP_MAX_BYTES // world)
+        del outputs
 
     sub = {}
-    if not args.no_sub:
+    if args.full and not args.no_sub:
         # the reference-default stop_rate 1 over a window of its own (--sr1-steps): its lagged stop checks keep up to
         # 8 checks in flight, so a 20-step window after a host synchronisation is mostly pipeline fill and drain
         k1, w1 = max(args.sr1_steps, args.steps), max(args.sr1_warmup, args.warmup)
@@ -1082,7 +1137,7 @@ def main():
             roof["launches_timed"] = launches
             roof["kernel_timer"] = "in_region" if args.kernel_timer_in_region else "post_region"
         cpu = None
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             v1, it1, dt1 = cpu_baseline(n0, n1, seed=1234, budget_s=args.cpu_seconds, threads=1)
             th = max(1, min(CPU_THREADS_MAX, os.cpu_count() or 1))
             vn, itn, dtn = cpu_baseline(n0, n1, seed=1234, budget_s=args.cpu_seconds, threads=th)

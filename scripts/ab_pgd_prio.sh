@@ -1,5 +1,5 @@
 export TMPDIR=/tmp; O=gpurun_out/${TAG:-r06b}; mkdir -p $O
-DRV="python3 bench.py --steps 20 --warmup 5 --no-sub --cpu-seconds 0"
+DRV="python3 bench.py --full --steps 20 --warmup 5 --no-sub --cpu-seconds 0"
 for i in 1 2; do
   for v in base ilp mem bias; do
     PXA_LIB_PATH=ab/libpyxu_amd_$v.so timeout -k 10 120 $DRV > $O/drv_${v}_$i.log 2>&1 || exit 1

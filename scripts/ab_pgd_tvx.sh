@@ -12,7 +12,7 @@ for k in a.files:
     print(k, 'bit-identical' if np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)) else 'DIFFER max %g' % np.max(np.abs(a[k] - b[k])))
 "
 PXA_LIB_PATH=ab/libpyxu_amd_tvx.so timeout -k 10 300 python -u -m pytest -q --timeout 120 --timeout-method thread -p no:cacheprovider -m gpu tests/test_gpu_pgd_variants.py tests/test_gpu_parity.py tests/test_gpu_bench_shapes.py -k "pgd or PGD or c2 or c5" > $O/tests.log 2>&1; tail -1 $O/tests.log
-DRV="python3 bench.py --steps 20 --warmup 5 --no-sub --cpu-seconds 0"
+DRV="python3 bench.py --full --steps 20 --warmup 5 --no-sub --cpu-seconds 0"
 for i in 1 2 3; do
   for v in base tvx; do
     PXA_LIB_PATH=ab/libpyxu_amd_$v.so timeout -k 10 120 $DRV > $O/drv_${v}_$i.log 2>&1 || exit 1

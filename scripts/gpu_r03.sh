@@ -23,7 +23,7 @@ if [ "$2" != "profonly" ]; then
 step variants 300 $PT tests/test_gpu_pgd_variants.py -m gpu
 [ "$2" = "quick" ] || step pytest 900 $PT tests -m gpu --ignore=tests/test_gpu_pgd_variants.py
 step smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-step bench 600 python bench.py
+step bench 600 python bench.py --full
 fi
 [ "$2" = "noprof" ] && { echo done; exit 0; }
 P=$O/prof

@@ -173,6 +173,6 @@ if [ "$S" = "full" ]; then
   step smoke 150 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$S" = "bench" ]; then
-  step bench 1000 python bench.py --steps 20 --warmup 5
+  step bench 1000 python bench.py --full --steps 20 --warmup 5
 fi
 echo done

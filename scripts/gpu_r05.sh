@@ -37,7 +37,7 @@ if [ "$S" = "new" ]; then
        tests/test_gpu_dense_normal.py tests/test_gpu_solver_engine.py
   step drv1 120 $DRV
   step trace 120 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- $DRV
-  step bench 900 python bench.py --steps 20 --warmup 5
+  step bench 900 python bench.py --full --steps 20 --warmup 5
 fi
 if [ "$S" = "admm" ]; then
   step admmtests 600 $PT -m gpu tests/test_gpu_admm_fused.py tests/test_gpu_dense_normal.py
@@ -79,7 +79,7 @@ if [ "$S" = "b" ]; then
   step drv1 120 $DRV
   step drv2 120 $DRV
   step trace 120 rocprofv3 --kernel-trace --stats -d $P/trace -o run --output-format csv -- $DRV
-  step bench 900 python bench.py --steps 20 --warmup 5
+  step bench 900 python bench.py --full --steps 20 --warmup 5
 fi
 if [ "$S" = "c" ]; then
   step tests 900 $PT -m gpu tests/test_gpu_fft.py tests/test_gpu_c3_fullsize.py tests/test_gpu_pds_fused.py tests/test_gpu_long_trajectories.py tests/test_gpu_bench_shapes.py
@@ -105,7 +105,7 @@ if [ "$S" = "e" ]; then
   step sr1prof 300 python3 scripts/prof_sr1.py
   step drv1 120 $DRV
   step drv2 120 $DRV
-  step bench 900 python bench.py --steps 20 --warmup 5
+  step bench 900 python bench.py --full --steps 20 --warmup 5
 fi
 if [ "$S" = "f" ]; then
   step foldtest 300 $PT -m gpu tests/test_gpu_pgd_variants.py
@@ -157,6 +157,6 @@ if [ "$S" = "full" ]; then
   step smoke 150 python -c "import __graft_entry__ as g; g.smoke()"
 fi
 if [ "$S" = "bench" ]; then
-  step bench 1000 python bench.py --steps 20 --warmup 5
+  step bench 1000 python bench.py --full --steps 20 --warmup 5
 fi
 echo done

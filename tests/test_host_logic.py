@@ -255,6 +255,23 @@ def test_bench_launcher_rank_envs_and_argv(tmp_path):
     assert bench.launch([], 2, script=str(bad)) == 3
 
 
+def test_bench_dump_outputs_whole_and_sampled(tmp_path):
+    """`bench.py --dump-outputs`: an array within the byte budget is written whole; a larger one as a
+    fixed, seeded sample of exactly the budget (the same elements in every run), float32 / float64 only."""
+    import bench
+
+    a = np.arange(1000, dtype=np.float32)
+    assert np.array_equal(bench.sample_output(a.reshape(10, 100), 4000), a)  # fits exactly: whole, flat
+    s1, s2 = bench.sample_output(a, 400), bench.sample_output(a.copy(), 400)
+    assert s1.dtype == np.float32 and s1.nbytes == 400 and np.array_equal(s1, s2)
+    assert np.all(np.diff(s1) > 0)  # distinct elements of `a`, in order
+    assert bench.sample_output(np.arange(5, dtype=np.int32), 1 << 20).dtype == np.float64
+    bench.dump_outputs(str(tmp_path / "d"), {"x": a, "big": np.ones(5000, np.float64)}, max_bytes=16000)
+    x, big = np.load(tmp_path / "d" / "x.npy"), np.load(tmp_path / "d" / "big.npy")
+    assert np.array_equal(x, a) and big.dtype == np.float64 and big.nbytes == 8000
+    assert bench.DUMP_MAX_BYTES <= 64 * 10**6 - 4096
+
+
 def test_threaded_cpu_baseline_is_the_oracle():
     """bench.py's all-core CPU baseline (oracle/parallel.py) computes the single-thread oracle's PGD
     iterates bit for bit."""
