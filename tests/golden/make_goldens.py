@@ -613,6 +613,57 @@ def gen_padselect():
         save(f"padselect_{w}", **out)
 
 
+def gen_asym():
+    """Asymmetric, per-axis different taps and per-axis sampling (tests/_asym_cases.py: the table the GPU tests of
+    the fused steps share): 2-D PGD, 2-D and 3-D PD3O / Condat-Vu, iterates after 1 and 10 iterations."""
+    sys.path.insert(0, os.path.join(HERE, "..", ".."))  # the table imports the oracle for its own helpers
+    sys.path.insert(0, os.path.join(HERE, ".."))
+    import _asym_cases as ac
+
+    def problem(e, dt):
+        kern = ac.kernels(e, dt)
+        y, x0 = ac.data(e, dt)
+        N = int(np.prod(e.shape))
+        S = pxo.Stencil(arg_shape=e.shape, kernel=kern, center=tuple(e.centers), mode="constant")
+        f = 0.5 * pxo.SquaredL2Norm(dim=N).asloss(y) * S
+        K = pxo.Gradient(arg_shape=e.shape, directions=e.dirs, sampling=e.sampling)
+        g = {"none": None, "pos": pxo.PositiveOrthant(dim=N), "l1": ac.G_L1 * pxo.L1Norm(dim=N)}[e.g]
+        common = dict(entry=e.name, g=e.g, tv=e.tv, arg_shape=np.array(e.shape), center=np.array(e.centers),
+                      sampling=np.array(e.sampling), y=y, x0=x0, **{f"kernel{a}": k for a, k in enumerate(kern)})
+        return f, K, g, N, x0, common
+
+    for name, w in (("onetile", "f32"),):
+        e, width = ac.BY_NAME[name], WIDTHS[w]
+        with pxrt.Precision(width):
+            f, K, g, N, x0, common = problem(e, width.value)
+            f = f + ac.PGD_LAM * pxo.L21Norm(arg_shape=(len(e.dirs), *e.shape)).moreau_envelope(ac.PGD_MU) * K
+            f.diff_lipschitz = ac.pgd_lipschitz(e)
+            res = {}
+            for n_it in (1, 10):
+                slvr = pxsl.PGD(f=f, g=g, show_progress=False)
+                slvr.fit(x0=x0, stop_crit=pxst.MaxIter(n_it))
+                res[f"x_{n_it}"] = slvr.solution()
+        save(f"asym_pgd_{name}_{w}", diff_lipschitz=ac.pgd_lipschitz(e), lam=ac.PGD_LAM, mu=ac.PGD_MU, **common, **res)
+
+    for name, w in (("tiny", "f64"), ("vol", "f32")):
+        e, width = ac.BY_NAME[name], WIDTHS[w]
+        with pxrt.Precision(width):
+            f, K, g, N, x0, common = problem(e, width.value)
+            f.diff_lipschitz = 1.0
+            Dd = len(e.dirs)
+            h = ac.PDS_LAM * (pxo.L21Norm(arg_shape=(Dd, *e.shape)) if e.tv == "iso" else pxo.L1Norm(dim=Dd * N))
+            res = {}
+            for algo, klass in (("pd3o", pxsl.PD3O), ("cv", pxsl.CondatVu)):
+                for n_it in (1, 10):
+                    slvr = klass(f=f, g=g, h=h, K=K, show_progress=False)
+                    slvr.fit(x0=x0, stop_crit=pxst.MaxIter(n_it))
+                    data, _ = slvr.stats()
+                    res[f"{algo}_x_{n_it}"], res[f"{algo}_z_{n_it}"] = data["x"], data["z"]
+                for k in ("tau", "sigma", "rho"):
+                    res[f"{algo}_{k}"] = slvr._mstate[k]
+        save(f"asym_pds_{name}_{w}", lam=ac.PDS_LAM, **common, **res)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1:  # e.g. `make_goldens.py diffops`: regenerate only the named families
         for name in sys.argv[1:]:
@@ -632,3 +683,4 @@ if __name__ == "__main__":
     gen_aliases()
     gen_padselect()
     gen_directional()
+    gen_asym()

@@ -287,12 +287,21 @@ def test_tv_dual_update_vs_oracle(dt, h_kind, sh, relax):
     assert rel_err(out, ref) <= TOL[dt], rel_err(out, ref)
 
 
+UNIT = ([-1.0] * 3, [1.0] * 3)
+PER_AXIS = ([-1 / 0.7, -1 / 1.9, -1 / 1.3], [1 / 0.7, 1 / 1.9, 1 / 1.3])
+
+
 @pytest.mark.parametrize("rows", [1, 2, 4, 8, 9])
 @pytest.mark.parametrize("dt", [np.float32, np.float64])
 @pytest.mark.parametrize("h_kind", ["l1", "iso"])
-@pytest.mark.parametrize("sh,stack", [((67, 129), 1), ((9, 33, 70), 1), ((5, 64, 128), 3), ((7, 37, 1024), 1),
-                                      ((3, 1, 64), 2), ((6, 19, 260), 2)], ids=lambda s: "x".join(map(str, s)) if isinstance(s, tuple) else str(s))
-def test_tv_dual_update_row_blocked_bit_exact(rows, dt, h_kind, sh, stack):
+@pytest.mark.parametrize("sh,stack,coefs", [
+    pytest.param((67, 129), 1, UNIT, id="67x129-1"), pytest.param((9, 33, 70), 1, UNIT, id="9x33x70-1"),
+    pytest.param((5, 64, 128), 3, UNIT, id="5x64x128-3"), pytest.param((7, 37, 1024), 1, UNIT, id="7x37x1024-1"),
+    pytest.param((3, 1, 64), 2, UNIT, id="3x1x64-2"), pytest.param((6, 19, 260), 2, UNIT, id="6x19x260-2"),
+    # a different forward-difference pair on every axis (sampling 0.7, 1.9, 1.3; D = 2 reads axes 1 and 2 only)
+    pytest.param((9, 33, 70), 1, PER_AXIS, id="9x33x70-1-per_axis"),
+    pytest.param((67, 129), 1, PER_AXIS, id="67x129-1-per_axis")])
+def test_tv_dual_update_row_blocked_bit_exact(rows, dt, h_kind, sh, stack, coefs):
     """Kernel C with `rows` rows of w per thread (PXA_TUNE_DUAL_ROWS; 1: the one-row kernel without its next-plane
     prefetch; 2, 4: a thread's row + 1 neighbours are its own rows;
     8: the plane-block kernel, whose row + 1 / column + 1 neighbours come from an LDS image of the block, 3-D fp32)
@@ -305,7 +314,7 @@ def test_tv_dual_update_row_blocked_bit_exact(rows, dt, h_kind, sh, stack):
     z = (0.05 * rng.standard_normal(stack * Dd * N)).astype(dt)
     geom = (stack, 1, *sh, 2) if Dd == 2 else (stack, *sh, 3)
     for relax in (0, 1):
-        args = (D(w), D(z), geom, [-1.0] * 3, [1.0] * 3, 0.37, 0.05, 0.7, 0 if h_kind == "l1" else 1)
+        args = (D(w), D(z), geom, *coefs, 0.37, 0.05, 0.7, 0 if h_kind == "l1" else 1)
         ref = to_NUMPY(_dev.tv_dual_update(*args, relax=relax))
         prev = _dev.tuning(_dev.TUNE_DUAL_ROWS, rows)
         try:

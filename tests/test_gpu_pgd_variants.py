@@ -32,24 +32,34 @@ from pyxu_amd import _dev  # noqa: E402
 from pyxu_amd._lib import lib  # noqa: E402
 from pyxu_amd.util import to_device, to_NUMPY  # noqa: E402
 
+import _asym_cases as ac  # noqa: E402
+
 
 def _problem(sh, y_images, sigma, g_kind, lam=0.02, mu=0.01, seed=0):
+    """sigma: the width of a Gaussian blur, or an entry of tests/_asym_cases.py (explicit per-axis taps and centres on
+    the two image axes, and its per-axis sampling)."""
     rng = np.random.default_rng(seed)
     N = int(np.prod(sh))
     y = rng.standard_normal(y_images * N).astype(np.float32)
     with pxrt.Precision(pxrt.Width.SINGLE):
-        if y_images == 1:
-            H = pxo.Gaussian(arg_shape=sh, sigma=sigma)
-            G = pxo.Gradient(arg_shape=sh)
-            dim = N
-            l21 = pxo.L21Norm(arg_shape=(2, *sh))
+        full = sh if y_images == 1 else (y_images, *sh)
+        dirs = (0, 1) if y_images == 1 else (1, 2)
+        if isinstance(sigma, ac.Entry):
+            assert sigma.shape[-2:] == tuple(sh)
+            lead = [np.array([1.0], np.float32)] * (len(full) - 2)
+            H = pxo.Stencil(arg_shape=full, kernel=lead + ac.kernels(sigma, np.float32)[-2:],
+                            center=[0] * len(lead) + list(sigma.centers[-2:]), mode="constant")
+            samp = (1.0,) * len(lead) + tuple(sigma.sampling[-2:])
+            G = pxo.Gradient(arg_shape=full, directions=dirs, sampling=samp)
+            L = 1 + 4 * lam / mu * sum(1 / h ** 2 for h in samp[-2:])
         else:
-            H = pxo.Gaussian(arg_shape=(y_images, *sh), sigma=(0, sigma, sigma))
-            G = pxo.Gradient(arg_shape=(y_images, *sh), directions=(1, 2))
-            dim = y_images * N
-            l21 = pxo.L21Norm(arg_shape=(2, y_images, *sh))
+            H = pxo.Gaussian(arg_shape=full, sigma=sigma if y_images == 1 else (0, sigma, sigma))
+            G = pxo.Gradient(arg_shape=full, directions=dirs)
+            L = 1 + 8 * lam / mu
+        dim = y_images * N
+        l21 = pxo.L21Norm(arg_shape=(2, *full))
         f = 0.5 * pxo.SquaredL2Norm(dim=dim).asloss(to_device(y)) * H + lam * l21.moreau_envelope(mu) * G
-        f.diff_lipschitz = 1 + 8 * lam / mu
+        f.diff_lipschitz = L
         g = {"none": None, "pos": pxo.PositiveOrthant(dim=dim), "l1": 0.01 * pxo.L1Norm(dim=dim)}[g_kind]
     return f, g, dim, rng
 
@@ -99,10 +109,18 @@ CASES = [
     ((128, 192), 3, 1, 2.0, "pos"),     # stacked initial points, one y
     ((64, 320), 4, 4, 1.5, "pos"),      # batch-as-axis: per-image data
     ((40, 36), 2, 2, 1.0, "none"),      # tiles larger than the image
+    # asymmetric, off-centre taps that differ per axis (R = 4), sampling (1.9, 0.7): 2 x 2 ragged tiles, one image ...
+    ((40, 68), 1, 1, ac.BY_NAME["vec"], "pos"),
+    ((40, 68), 3, 3, ac.BY_NAME["vec"], "l1"),  # ... and batch-as-axis
 ]
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0][0]}x{c[0][1]}-s{c[1]}-y{c[2]}-sig{c[3]}-{c[4]}")
+def _cid(c):
+    sig = f"asym_{c[3].name}" if isinstance(c[3], ac.Entry) else c[3]
+    return f"{c[0][0]}x{c[0][1]}-s{c[1]}-y{c[2]}-sig{sig}-{c[4]}"
+
+
+@pytest.mark.parametrize("case", CASES, ids=_cid)
 def test_vector_and_scalar_paths_bit_exact(case):
     """Aligned arrays (16-B vector loads / stores, also on the edge tiles' inside vectors) against
     misaligned copies (every access scalar): x_new and the RelError partials bit for bit; a launch
@@ -209,7 +227,7 @@ def _with_kernel(v, fn):
         _dev.tuning(0, old)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0][0]}x{c[0][1]}-s{c[1]}-y{c[2]}-sig{c[3]}-{c[4]}")
+@pytest.mark.parametrize("case", CASES, ids=_cid)
 def test_strip_kernel_matches_tile_kernel(case):
     """The strip kernel (PXA_TUNE_PGD_KERNEL = strip length; opt-in, measured slower) against the tile kernel:
     x_new and the RelError partials bit for bit, for strips of 2 and 3 tiles and whole-column strips (the top,
@@ -279,7 +297,7 @@ def _with_pipe(on, fn):
         _dev.tuning(_dev.TUNE_PGD_PIPE, old)
 
 
-@pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0][0]}x{c[0][1]}-s{c[1]}-y{c[2]}-sig{c[3]}-{c[4]}")
+@pytest.mark.parametrize("case", CASES, ids=_cid)
 def test_pipe_kernel_matches_tile_kernel(case):
     """The pipelined kernel (PXA_TUNE_PGD_PIPE = 1; opt-in, measured slower: resident workgroups, the next tile's window
     fetched by LDS-DMA during the current tile) against the tile kernel: x_new and the RelError partials bit for bit,

@@ -25,11 +25,22 @@ import pyxu_amd.opt.stop as pxst  # noqa: E402
 import pyxu_amd.runtime as pxrt  # noqa: E402
 from pyxu_amd.util import to_device, to_NUMPY  # noqa: E402
 
+import _asym_cases as ac  # noqa: E402
 
-def _problem(sh=(96, 128), stack=1):
+
+def _problem(sh=(96, 128), stack=1, entry=None):
     rng = np.random.default_rng(3)
-    N = int(np.prod(sh))
     lam, mu = 0.02, 0.01
+    if entry is not None:  # an entry of tests/_asym_cases.py: asymmetric per-axis taps, per-axis sampling
+        sh = entry.shape
+        N = int(np.prod(sh))
+        y = rng.standard_normal(N).astype(np.float32)
+        H = pxo.Stencil(arg_shape=sh, kernel=ac.kernels(entry, np.float32), center=list(entry.centers), mode="constant")
+        G = pxo.Gradient(arg_shape=sh, sampling=entry.sampling)
+        f = 0.5 * pxo.SquaredL2Norm(dim=N).asloss(to_device(y)) * H + lam * pxo.L21Norm(arg_shape=(2, *sh)).moreau_envelope(mu) * G
+        f.diff_lipschitz = 1 + 4 * lam / mu * sum(1 / h ** 2 for h in entry.sampling)
+        return f, pxo.PositiveOrthant(dim=N), N
+    N = int(np.prod(sh))
     y = rng.standard_normal(stack * N).astype(np.float32)
     if stack == 1:
         H = pxo.Gaussian(arg_shape=sh, sigma=1.5)
@@ -45,7 +56,7 @@ def _problem(sh=(96, 128), stack=1):
 
 
 def _run(lagged, crit_fn, mode, monkeypatch, tmp_path, tag, depth=8, inkernel=False, pieces=None, stack=1, window=True,
-         pub=True):
+         pub=True, entry=None):
     monkeypatch.setattr(pxa.Solver, "_LAG", depth if lagged else 0)
     monkeypatch.setattr(pxa.Solver, "_LAG_INKERNEL", inkernel)
     monkeypatch.setattr(pxa.Solver, "_LAG_WINDOW", window)
@@ -54,7 +65,7 @@ def _run(lagged, crit_fn, mode, monkeypatch, tmp_path, tag, depth=8, inkernel=Fa
         monkeypatch.setattr(pxs.PGD, "_spec_supported", lambda self: False)
     monkeypatch.setattr(pxa.Solver, "_LAG_INKERNEL", inkernel)
     with pxrt.Precision(pxrt.Width.SINGLE):
-        f, g, N = _problem(stack=stack)
+        f, g, N = _problem(stack=stack, entry=entry)
         s = pxs.PGD(f=f, g=g, show_progress=False, stop_rate=1, folder=tmp_path / tag)
         x0 = to_device(np.zeros(N, np.float32))
         items, stats_eq = [], True
@@ -119,6 +130,17 @@ def test_lagged_checks_maxiter_stop_and_depths(depth, monkeypatch, tmp_path):
     crit = lambda: pxst.RelError(eps=1e-9) | pxst.MaxIter(37)  # noqa: E731
     a = _run(True, crit, "MANUAL", monkeypatch, tmp_path, "lag", depth=depth, stack=3)
     b = _run(False, crit, "MANUAL", monkeypatch, tmp_path, "sync", stack=3)
+    assert b["idx"] == 37 and b["hist"]["N_iter"][-1] == 38
+    _same(a, b, exact_rel=False)
+
+
+def test_lagged_checks_asymmetric_taps(monkeypatch, tmp_path):
+    """Lag depth 3 on asymmetric, per-axis different taps and sampling ((40, 68): 2 x 2 tiles; the window statistics
+    and the publishing workgroup run beside the boundary-row corrections): MaxIter fires first."""
+    crit = lambda: pxst.RelError(eps=1e-9) | pxst.MaxIter(37)  # noqa: E731
+    e = ac.BY_NAME["vec"]
+    a = _run(True, crit, "MANUAL", monkeypatch, tmp_path, "lag", depth=3, entry=e)
+    b = _run(False, crit, "MANUAL", monkeypatch, tmp_path, "sync", entry=e)
     assert b["idx"] == 37 and b["hist"]["N_iter"][-1] == 38
     _same(a, b, exact_rel=False)
 
