@@ -33,6 +33,7 @@
 // bank model (scripts/ldsbank.py).  The blockIdx -> tile map is XCD-aware: each of the 8 XCDs owns a
 // contiguous band of tiles so that halo re-reads of x / x_prev hit its own L2.
 #include "tile2d.hpp"
+#include <type_traits>
 
 // Wave priority (s_setprio) of the window-load phase: its loads issue ahead of the passes of the other
 // workgroups resident on the SIMD, so that the next round's windows are in flight sooner.  Interleaved A/B
@@ -136,79 +137,146 @@ __device__ inline float tv_weight<float>(float n2, float lam, float mu, float in
 // ---- phase 0 of the tile kernel: yk = (x - x_prev) * a + x on the A window, zero outside the image.
 // All K0 vector pairs of a thread are loaded before the first LDS store, so their latencies overlap.
 // `lt`: the thread's index among the kThreads threads that share the window.
+//
+// Window order.  Thread (wave wv, lane ln) handles item k = 0 .. K0 - 1; window vector (row r, vector column g) of
+// an item is a LANE part (rl, gl), a function of ln alone and the same for every item of a region, plus a
+// WAVE-UNIFORM part (ru, gu), a function of k and wv: no per-item division, and every region choice is a scalar
+// branch or resolved at compile time.
+//   items k < KI     the tile's own TY x TX pixels, row-major: item k is item 0 shifted down by kThreads / TV rows.
+//                    The RelError window partials (the tile's pixels only) are exactly these items of every thread.
+//   halo wave-slots  hs = (k - KI) * NW + wv, in two regions with wave-aligned boundaries:
+//     side  (hs < NSS)   the CV vectors left and right of ALL AR window rows.  Row-block form: a slot takes 64 / (2 CV)
+//                        whole rows (lane -> row ln / (2 CV), side vector ln % (2 CV), once per thread), successive
+//                        slots are that many rows apart.  Where the row blocks would need more slots than K0 leaves
+//                        (fp64, R = 7) the column form: slot = side vector column, lane = window row.
+//     vert  (< NSS+NVS)  the TV tile-column vectors of the 2R rows above and the 2R rows below the tile: 64 / TV rows
+//                        per slot, alternately from the top and the bottom block (lane -> ln / TV: even top, odd
+//                        bottom), successive slots 64 / TV / 2 rows further down in both blocks.
+// Lanes of a side slot beyond its rows, and the slots beyond NSS + NVS, are idle.  Any bijection of window vectors to
+// (thread, item) gives the same A (each vector's yk is computed alone): the order only moves work between threads.
 template <typename T, int R>
 struct Window {
   using L = Layout<T, R>;
   static constexpr int K0 = cdiv(L::N0, kThreads);
-  // the tile's own vectors come first (thread-uniform: items k < KI of every thread), then the halo
-  static constexpr int NI = TY * (TX / L::V);
+  static constexpr int NW = kThreads / 64;
+  static constexpr int TV = TX / L::V, CV = L::CA / L::V;
+  static constexpr int NI = TY * TV;
   static constexpr int KI = NI / kThreads;
+  static constexpr int RPI = kThreads / TV;  // tile rows per own item
+  static constexpr int RPW = 64 / TV;        // rows per wave (own items) / per vert slot
+  static constexpr int SL = 2 * CV;          // side vectors per window row
+  static constexpr int SRB = 64 / SL;        // side, row-block form: rows per slot
+  static constexpr int NVS = 4 * R / RPW;    // vert slots
+  static constexpr int HS = (K0 - KI) * NW;  // halo wave-slots that K0 items leave
+  static constexpr bool SIDE_ROWS = cdiv(L::AR, SRB) + NVS <= HS;
+  static constexpr int NSS = SIDE_ROWS ? cdiv(L::AR, SRB) : SL;  // side slots
+  static constexpr int NSLOT = KI * NW + NSS + NVS;              // wave-slots in use
   static_assert(NI % kThreads == 0, "every thread loads KI of the tile's own vectors");
+  static_assert(64 % TV == 0 && RPW % 2 == 0 && (4 * R) % RPW == 0, "vert slots: whole rows, top / bottom pairs");
+  static_assert(SL <= 64 && L::AR <= 64, "side slots: a row block or a column per wave");
+  static_assert(NSS + NVS <= HS, "K0 must not grow");
+
+  // item k of lane ln in wave wv -> window row rl + ru, vector column gl + gu; false: an idle slot
+  __host__ __device__ static constexpr bool item(int k, int wv, int ln, int& rl, int& gl, int& ru, int& gu) {
+    rl = gl = ru = gu = 0;
+    if (k < KI) {
+      rl = 2 * R + ln / TV;
+      gl = CV + ln % TV;
+      ru = k * RPI + wv * RPW;
+      return true;
+    }
+    const int hs = (k - KI) * NW + wv;
+    if (hs < NSS) {
+      if (SIDE_ROWS) {
+        const int q = ln % SL;
+        rl = ln / SL;
+        gl = q < CV ? q : q + TV;
+        ru = hs * SRB;
+        return ln < SRB * SL && rl + ru < L::AR;
+      }
+      rl = ln;
+      gu = hs < CV ? hs : hs + TV;
+      return ln < L::AR;
+    }
+    if (hs < NSS + NVS) {
+      const int j = ln / TV;
+      rl = (j >> 1) + (j & 1) * (2 * R + TY);
+      gl = CV + ln % TV;
+      ru = (hs - NSS) * (RPW / 2);
+      return true;
+    }
+    return false;
+  }
+  // every one of the N0 window vectors is item (k, wv, ln) of exactly one thread
+  static constexpr bool covers_once() {
+    int cnt[L::N0] = {};
+    for (int k = 0; k < K0; ++k)
+      for (int wv = 0; wv < NW; ++wv)
+        for (int ln = 0; ln < 64; ++ln) {
+          int rl = 0, gl = 0, ru = 0, gu = 0;
+          if (!item(k, wv, ln, rl, gl, ru, gu)) continue;
+          const int r = rl + ru, g = gl + gu;
+          if (r < 0 || r >= L::AR || g < 0 || g >= L::NGA) return false;
+          ++cnt[r * L::NGA + g];
+        }
+    for (int i = 0; i < L::N0; ++i)
+      if (cnt[i] != 1) return false;
+    return true;
+  }
+  static_assert(covers_once(), "the window order is a bijection onto the AR x NGA window vectors");
+
   T xv[K0][L::V], pv[K0][L::V];
 };
 
-// Window vector `it` (0 .. N0) -> window row r, vector column g.  Items 0 .. NI - 1 are the tile's own TY x TX pixels
-// (row-major), the rest the halo: the top 2R rows, then the CA / V vectors left and right of each tile row, then the
-// bottom 2R rows.  So the RelError window partials (the tile's pixels only) are items k < KI of every thread: no
-// divergent double-precision code (the row-major order spread them over all K0 items, exec-masked).  Any bijection
-// gives the same A (each vector's yk is computed alone): the order only moves work between threads.
-#ifndef PXA_PGD_WIN_ROWMAJOR
-#define PXA_PGD_WIN_ROWMAJOR 0  // (A/B builds: the row-major window order of rounds 1-5)
-#endif
-template <typename T, int R>
-__device__ inline void win_rg(int it, int& r, int& g) {
-  using L = Layout<T, R>;
-  if (PXA_PGD_WIN_ROWMAJOR) {
-    r = it / L::NGA;
-    g = it - r * L::NGA;
-    return;
-  }
-  constexpr int TV = TX / L::V, CV = L::CA / L::V, NI = Window<T, R>::NI;
-  constexpr int TOP = 2 * R * L::NGA, MID = TY * 2 * CV;
-  if (it < NI) {
-    r = 2 * R + it / TV;
-    g = CV + it % TV;
-    return;
-  }
-  const int h = it - NI;
-  if (h < TOP) {
-    r = h / L::NGA;
-    g = h - r * L::NGA;
-  } else if (h < TOP + MID) {
-    const int m = h - TOP, q = m % (2 * CV);
-    r = 2 * R + m / (2 * CV);
-    g = q < CV ? q : q + TV;
-  } else {
-    const int b = h - TOP - MID, rb = b / L::NGA;
-    r = 2 * R + TY + rb;
-    g = b - rb * L::NGA;
-  }
+// (wave, lane) of thread lt; the wave index as a scalar, so that what Window::item derives from it is wave-uniform.
+// This is all the range knowledge the window decode needs (lane < 64 by the mask, wave < 4 by the assume).  A range
+// assumption on the thread index itself, visible to the passes and the epilogue too, removed nothing more from the fp32
+// kernel and made every fp64 instantiation spill (R = 2 .. 8: 108 .. 1284 B of scratch per thread), so there is none.
+__device__ inline void wave_lane(int lt, int& wv, int& ln) {
+  wv = __builtin_amdgcn_readfirstlane(lt >> 6);
+  __builtin_assume(wv >= 0 && wv < kThreads / 64);
+  ln = lt & 63;
+}
+
+// Interior tiles: the address of a vector as a wave-uniform 64-bit base -- element (row0 + ru, col0) of the image,
+// formed in scalar registers -- plus a zero-extended 32-bit byte offset per lane (the saddr + voffset form of the
+// global loads / stores: no 64-bit address arithmetic in the vector unit).  The kernels' `interior` predicate bounds
+// n1 so that the lane offsets, at most (AR n1 + AC) sizeof(T), fit in 32 bits.
+constexpr int kMaxInteriorN1 = 1 << 22;  // (64 rows x 2^22 columns x 8 B = 2^31)
+template <typename T>
+__device__ inline T* lane_ptr(T* img, int row0, int col0, int n1, int ru, unsigned voff) {
+  T* base = img + ((int64_t)row0 * n1 + col0) + ru * n1;  // (ru n1 < 2^28: |ru| <= 64, n1 <= kMaxInteriorN1)
+  using C = std::conditional_t<std::is_const_v<T>, const char, char>;
+  return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + (size_t)voff);
 }
 
 template <typename T, int R, bool EDGE>
 __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const T* __restrict__ xs,
                                  const T* __restrict__ xps, Window<T, R>& w, int lt) {
   using L = Layout<T, R>;
+  using W = Window<T, R>;
   constexpr int V = L::V;
   constexpr int CA = L::CA;
   const int n0 = p.n0, n1 = p.n1;
+  int wv, ln;
+  wave_lane(lt, wv, ln);
 #pragma unroll
-  for (int k = 0; k < Window<T, R>::K0; ++k) {
-    const int it = lt + k * kThreads;
-    if (it < L::N0) {
-      int r, g;
-      win_rg<T, R>(it, r, g);
-      const int gr = ty0 - 2 * R + r, gc = tx0 - CA + V * g;
+  for (int k = 0; k < W::K0; ++k) {
+    int rl, gl, ru, gu;
+    if (W::item(k, wv, ln, rl, gl, ru, gu)) {
       if (!EDGE) {
-        const unsigned off = (unsigned)(gr * n1 + gc);
-        ld_vec<T, V>(xs + off, w.xv[k]);
+        const unsigned voff = (unsigned)(rl * n1 + V * gl) * (unsigned)sizeof(T);
+        ld_vec<T, V>(lane_ptr<const T>(xs, ty0 - 2 * R, tx0 - CA + V * gu, n1, ru, voff), w.xv[k]);
         if (kProbes && (p.diag & 256)) {  // timing probe only (WRONG results): one window array instead of two
 #pragma unroll
           for (int v = 0; v < V; ++v) w.pv[k][v] = w.xv[k][v];
         } else {
-          ld_vec<T, V>(xps + off, w.pv[k]);
+          ld_vec<T, V>(lane_ptr<const T>(xps, ty0 - 2 * R, tx0 - CA + V * gu, n1, ru, voff), w.pv[k]);
         }
-      } else if (gr >= 0 && gr < n0 && p.vec_ok && gc >= 0 && gc + V <= n1) {
+        continue;
+      }
+      const int gr = ty0 - 2 * R + rl + ru, gc = tx0 - CA + V * (gl + gu);
+      if (gr >= 0 && gr < n0 && p.vec_ok && gc >= 0 && gc + V <= n1) {
         ld_vec<T, V>(xs + (int64_t)gr * n1 + gc, w.xv[k]);
         ld_vec<T, V>(xps + (int64_t)gr * n1 + gc, w.pv[k]);
       } else {
@@ -226,17 +294,18 @@ __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const 
 template <typename T, int R>
 __device__ inline void win_store(const PgdParams<T>& p, T* A, const Window<T, R>& w, int lt) {
   using L = Layout<T, R>;
+  using W = Window<T, R>;
   constexpr int V = L::V;
+  int wv, ln;
+  wave_lane(lt, wv, ln);
 #pragma unroll
-  for (int k = 0; k < Window<T, R>::K0; ++k) {
-    const int it = lt + k * kThreads;
-    if (it < L::N0) {
-      int r, g;
-      win_rg<T, R>(it, r, g);
+  for (int k = 0; k < W::K0; ++k) {
+    int rl, gl, ru, gu;
+    if (W::item(k, wv, ln, rl, gl, ru, gu)) {
       T out[V];
 #pragma unroll
       for (int v = 0; v < V; ++v) out[v] = fma(w.xv[k][v] - w.pv[k][v], p.a, w.xv[k][v]);  // one rounding site
-      st_vec<T, V>(A + r * L::AP + V * g, out);
+      st_vec<T, V>(A + (rl * L::AP + V * gl) + (ru * L::AP + V * gu), out);
     }
   }
 }
@@ -245,8 +314,9 @@ template <typename T, int R, bool EDGE>
 __device__ inline void load_window(const PgdParams<T>& p, T* A, int ty0, int tx0, const T* __restrict__ xs,
                                    const T* __restrict__ xps) {
   Window<T, R> w;
-  win_issue<T, R, EDGE>(p, ty0, tx0, xs, xps, w, threadIdx.x);
-  win_store<T, R>(p, A, w, threadIdx.x);
+  const int tid = threadIdx.x;
+  win_issue<T, R, EDGE>(p, ty0, tx0, xs, xps, w, tid);
+  win_store<T, R>(p, A, w, tid);
 }
 
 // ---- pass A: PT[col][row] = (G0 yk)[row][col] for the TY tile rows and all A columns
@@ -504,6 +574,14 @@ __device__ inline bool vec_inside(const PgdParams<T>& p, int gr, int gc) {
   return p.vec_ok && gr < p.n0 && gc + kVecN<T> <= p.n1;
 }
 
+// byte offset of the row-major epilogue lane's vector of sweep s (Stage::lane: tile row r0 + s RPS, vector cq) from
+// the tile's first pixel.  The sweep's row shift is added here, in 32 bits (one add per sweep, shared by the H^T y / x
+// loads and the x_new store): as a shift of the uniform base the compiler re-associated it into 64-bit vector adds.
+template <typename T, int R>
+__device__ inline unsigned stage_voff(int r0, int cq, int n1, int s) {
+  return (unsigned)((r0 + s * Stage<T, R>::RPS) * n1 + kVecN<T> * cq) * (unsigned)sizeof(T);
+}
+
 template <typename T, int R, bool EDGE>
 __device__ inline void load_staged(const PgdParams<T>& p, int ty0, int tx0, const T* __restrict__ src, T (&v)[StagedB<T, R>::NS][kVecN<T>],
                                    int lt = threadIdx.x) {
@@ -515,8 +593,8 @@ __device__ inline void load_staged(const PgdParams<T>& p, int ty0, int tx0, cons
 #pragma unroll
   for (int s = 0; s < StagedB<T, R>::NS; ++s) {  // all loads first: one round trip
     const int gr = ty0 + r0 + s * S::RPS, gc = tx0 + V * cq;
-    if (!EDGE) {
-      ld_vec<T, V>(src + (unsigned)(gr * n1 + gc), v[s]);
+    if (!EDGE) {  // (uniform base + 32-bit lane offset: lane_ptr)
+      ld_vec<T, V>(lane_ptr<const T>(src, ty0, tx0, n1, 0, stage_voff<T, R>(r0, cq, n1, s)), v[s]);
     } else if (vec_inside(p, gr, gc)) {  // edge tile, but this vector is inside: one 16-B load
       ld_vec<T, V>(src + (int64_t)gr * n1 + gc, v[s]);
     } else {
@@ -527,10 +605,10 @@ __device__ inline void load_staged(const PgdParams<T>& p, int ty0, int tx0, cons
 }
 
 // z = ((G yk + Grad^T q) - H^T y) * (-tau) + yk; x_new = prox(z); RelError partials sum (x_new - x)^2,
-// sum x^2 in double.  One 16-B vector of one tile row.
+// sum x^2 in double.  One 16-B vector of one tile row; `vdst`: its address in x_new (interior tiles: from lane_ptr).
 template <typename T, bool EDGE>
 __device__ inline void finish_vec(const PgdParams<T>& p, int gr, int gc, const T (&g)[kVecN<T>], const T (&bv)[kVecN<T>],
-                                  const T (&yc)[kVecN<T>], const T (&xv)[kVecN<T>], T* __restrict__ xns,
+                                  const T (&yc)[kVecN<T>], const T (&xv)[kVecN<T>], T* __restrict__ xns, T* vdst,
                                   bool want_part, double& part_d, double& part_x) {
   constexpr int V = kVecN<T>;
   const int n0 = p.n0, n1 = p.n1;
@@ -543,7 +621,7 @@ __device__ inline void finish_vec(const PgdParams<T>& p, int gr, int gc, const T
   }
   const bool whole = !EDGE || vec_inside(p, gr, gc);
   if (whole) {
-    st_vec<T, V>(xns + (EDGE ? (int64_t)gr * n1 + gc : (int64_t)(unsigned)(gr * n1 + gc)), xo);
+    st_vec<T, V>(EDGE ? xns + ((int64_t)gr * n1 + gc) : vdst, xo);
     if (want_part) {
 #pragma unroll
       for (int w = 0; w < V; ++w) {
@@ -728,7 +806,8 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
         if (g[0] + y[0] + hb.v[s][0] == T(-12345)) xns[0] = T(0);  // keeps the loads and the O / A reads
         continue;
       }
-      finish_vec<T, EDGE>(p, ty0 + r, tx0 + V * cq, g, hb.v[s], y, hb.x[s], xns, want_part, part_d, part_x);
+      T* vdst = EDGE ? nullptr : lane_ptr<T>(xns, ty0, tx0, n1, 0, stage_voff<T, R>(r0, cq, n1, s));
+      finish_vec<T, EDGE>(p, ty0 + r, tx0 + V * cq, g, hb.v[s], y, hb.x[s], xns, vdst, want_part, part_d, part_x);
     }
   }
   tmark(7);
@@ -749,20 +828,12 @@ __device__ inline void win_partials(const Window<T, R>& w, double* __restrict__ 
   using L = Layout<T, R>;
   double part_d = 0.0, part_x = 0.0;
 #pragma unroll
-  for (int k = 0; k < (PXA_PGD_WIN_ROWMAJOR ? Window<T, R>::K0 : Window<T, R>::KI); ++k) {  // (items k < KI: the tile's own vectors, win_rg)
-    int r = 2 * R, g = L::CA / L::V;
-    if (PXA_PGD_WIN_ROWMAJOR) {
-      const int it = tid + k * kThreads;
-      if (it >= L::N0) continue;
-      win_rg<T, R>(it, r, g);
-    }
-    if (r >= 2 * R && r < 2 * R + TY && L::V * g >= L::CA && L::V * g < L::CA + TX) {
+  for (int k = 0; k < Window<T, R>::KI; ++k) {  // (items k < KI: the tile's own vectors, Window::item)
 #pragma unroll
-      for (int v = 0; v < L::V; ++v) {
-        const double dd = (double)w.xv[k][v] - (double)w.pv[k][v];
-        part_d = fma(dd, dd, part_d);
-        part_x = fma((double)w.pv[k][v], (double)w.pv[k][v], part_x);
-      }
+    for (int v = 0; v < L::V; ++v) {
+      const double dd = (double)w.xv[k][v] - (double)w.pv[k][v];
+      part_d = fma(dd, dd, part_d);
+      part_x = fma((double)w.pv[k][v], (double)w.pv[k][v], part_x);
     }
   }
   // (DPP wave sums: the __shfl_down ladder of wave_partials is a chain of twelve LDS round trips, on the path to the
@@ -811,8 +882,14 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
 #endif
   tmark(1);
   __syncthreads();
+  // fp64: the thread index laundered between the window and the body (as the strip kernel does per tile), so that the
+  // body derives its lane values afresh instead of sharing them with the window phase and keeping them live across it:
+  // no scratch up to R = 6 and 84-117 VGPRs where sharing them spilled (profiles/pgd_window_isa.txt).  fp32 shares them:
+  // laundering there costs ~30 static VALU and changes nothing at R <= 6.
+  int btid = tid;
+  if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(btid));
   pgd_tile_body<T, R, EDGE, PXA_PGD_SWEEP_DEPTH, false>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
-                                                 nullptr, NoHook{}, tid);
+                                                 nullptr, NoHook{}, btid);
 }
 
 // (Opt-in: PXA_RELERR_SINK=1; gfx950-specific.)  The hand-off below uses no release / acquire: it is the first row
@@ -916,8 +993,9 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
   T* xns = xn + (int64_t)s * img;
   const T* xrs = (p.xref != nullptr ? p.xref : x) + (int64_t)s * img;
   // interior: the whole A window lies inside the image (so no boundary rows / columns of G either),
-  // rows are 16-B aligned and 32-bit offsets suffice -> no bounds tests
-  const bool interior = p.vec_ok && img <= 0x7fffffff && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 &&
+  // rows are 16-B aligned and a lane's 32-bit byte offset from the tile's window origin suffices (lane_ptr:
+  // at most (AR n1 + AC) sizeof(T) < 2^32 for n1 <= kMaxInteriorN1) -> no bounds tests
+  const bool interior = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 &&
                         tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;
   if (interior)
     pgd_tile<T, R, false>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
@@ -1051,7 +1129,7 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_strip_kernel(PgdParams<T> p, 
   T* xns = xn + (int64_t)si * img;
   const T* xrs = (p.xref != nullptr ? p.xref : x) + (int64_t)si * img;
   const unsigned tpi = (unsigned)p.tiles0 * tiles1;
-  const bool cols_in = p.vec_ok && img <= 0x7fffffff && tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;
+  const bool cols_in = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;
   {
     const int ty0 = tr0 * TY;
 #if PXA_PGD_PRIO
@@ -1111,7 +1189,7 @@ int launch_pgd_strip(const PgdParams<T>& p, const void* x, const void* xp, const
 // 40 KB = 75.5 KB per workgroup (fp32, R = 6), two per CU; edge tiles are fetched with clamped addresses and their
 // outside vectors zeroed (vec_ok: a 16-B vector lies wholly inside or outside the image).
 template <typename T, int R>
-constexpr int kPipeChunks = cdiv(Layout<T, R>::N0, 64);  // one LDS-DMA wave-instruction = 64 window vectors
+constexpr int kPipeChunks = Window<T, R>::NSLOT;  // one LDS-DMA wave-instruction = one wave-slot of the window order
 template <typename T, int R>
 constexpr size_t kPipeArr = (size_t)kPipeChunks<T, R> * 64 * 16;  // bytes of one staged window array
 template <typename T, int R>
@@ -1126,16 +1204,16 @@ __device__ inline void pipe_issue(const PgdParams<T>& p, unsigned char* raw, int
   constexpr int V = L::V;
   constexpr int NW = kThreads / 64;
   static_assert(V * sizeof(T) == 16, "one 16-B vector per lane");
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  int wv, ln;
+  wave_lane(tid, wv, ln);
   const int n0 = p.n0, n1 = p.n1;
 #pragma unroll
   for (int k = 0; k < cdiv(kPipeChunks<T, R>, NW); ++k) {
-    const int c = wv + NW * k;
+    const int c = wv + NW * k;  // wave-slot = item k of this wave (Window::item)
     if (c < kPipeChunks<T, R>) {
-      int it = c * 64 + lane;
-      if (it >= L::N0) it = L::N0 - 1;  // (the last piece's surplus lanes fill the staging padding)
-      int r, g;
-      win_rg<T, R>(it, r, g);
+      int rl, gl, ru, gu;
+      (void)Window<T, R>::item(k, wv, ln, rl, gl, ru, gu);  // (idle lanes: clamped like the rest, dropped by pipe_window)
+      const int r = rl + ru, g = gl + gu;
       int gr = ty0 - 2 * R + r, gc = tx0 - L::CA + V * g;
       gr = gr < 0 ? 0 : gr >= n0 ? n0 - 1 : gr;
       gc = gc < 0 ? 0 : gc > n1 - V ? n1 - V : gc;
@@ -1159,13 +1237,14 @@ __device__ inline void pipe_window(const PgdParams<T>& p, T* A, const unsigned c
   const T* rx = reinterpret_cast<const T*>(raw);
   const T* rp = reinterpret_cast<const T*>(raw + kPipeArr<T, R>);
   Window<T, R> w;
+  int wv, ln;
+  wave_lane(tid, wv, ln);
 #pragma unroll
   for (int k = 0; k < Window<T, R>::K0; ++k) {
-    const int it = tid + k * kThreads;
-    if (it < L::N0) {
-      int r, g;
-      win_rg<T, R>(it, r, g);
-      const int gr = ty0 - 2 * R + r, gc = tx0 - L::CA + V * g;
+    const int it = tid + k * kThreads;  // staged vector of wave-slot wv + NW k, lane ln
+    int rl, gl, ru, gu;
+    if (Window<T, R>::item(k, wv, ln, rl, gl, ru, gu)) {
+      const int gr = ty0 - 2 * R + rl + ru, gc = tx0 - L::CA + V * (gl + gu);
       ld_vec<T, V>(rx + V * it, w.xv[k]);
       ld_vec<T, V>(rp + V * it, w.pv[k]);
       if (!(gr >= 0 && gr < n0 && gc >= 0 && gc < n1)) {
@@ -1239,7 +1318,7 @@ __global__ void __launch_bounds__(kThreads, 2) pgd_pipe_kernel(PgdParams<T> p, c
     const T* bs = b + (int64_t)(si % (unsigned)p.y_images) * img;
     T* xns = xn + (int64_t)si * img;
     const T* xrs = (p.xref != nullptr ? p.xref : x) + (int64_t)si * img;
-    const bool interior = img <= 0x7fffffff && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 && tx0 - L::CA >= 0 &&
+    const bool interior = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 && tx0 - L::CA >= 0 &&
                           tx0 + TX + L::CA <= p.n1;
     double* bp = p.win_part ? nullptr : partials;
     if (interior)
