@@ -117,7 +117,7 @@ extern "C" {
 #define PXA_RED_DIFFSQ 1 /* sum (x-y)^2        : RelError numerator (opt/stop.py:365-371) */
 #define PXA_RED_DOT 2    /* sum x*y            : CG alpha denominator (opt/solver/cg.py:130) */
 #define PXA_RED_ABS 3    /* sum |x|            : L1Norm.apply (norm.py:42-45) */
-#define PXA_RED_MAXABS 4 /* max |x|            : LInfinityNorm / norm(ord=inf) */
+#define PXA_RED_MAXABS 4 /* max |x| (NaN-propagating, numpy.linalg.norm(ord=inf)) : LInfinityNorm / norm(ord=inf) */
 #define PXA_RED_SUM 5    /* sum x              : Sum / QuadraticFunc.apply (operator.py:1255-1262) */
 #define PXA_RED_NEGCNT 6 /* count(x < 0)       : PositiveOrthant.apply (func/indicator.py:198-202) */
 #define PXA_RED_MIN 7    /* min x (NaN-propagating, numpy.min) : Memorize.info (opt/stop.py:181-196) */

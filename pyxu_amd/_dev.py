@@ -756,7 +756,7 @@ def row_reduce(op, x, y=None, out=None):
     torch = _torch()
     x = require(x)
     n = x.shape[-1] if x.ndim > 0 else 1
-    rows = x.numel() // max(n, 1) if x.numel() else 0
+    rows = int(np.prod(x.shape[:-1])) if x.ndim > 1 else 1  # rows of zero elements reduce to 0 (pxa_row_reduce)
     if y is not None:
         y = require(y)
         assert y.shape == x.shape
@@ -764,8 +764,9 @@ def row_reduce(op, x, y=None, out=None):
         out = torch.empty((max(rows, 1),), dtype=torch.float64, device=x.device)
     else:
         assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == max(rows, 1)
-    if rows == 0:
-        return out.zero_()
+    if x.numel() == 0:  # no rows, or rows without elements: the statistic of an empty row is 0
+        out.zero_()
+        return out.reshape(x.shape[:-1]) if x.ndim > 1 and rows > 0 else out
     # rows beyond the grid-y limit are processed in slabs
     step = 65535
     for r0 in range(0, rows, step):
@@ -784,18 +785,22 @@ def row_reduce(op, x, y=None, out=None):
 
 
 def row_reduce_pow(p, x, y=None, out=None):
-    """Per-row sum |x - y|^p (p > 0) or non-zero count (p == 0) -> float64 device (rows,) tensor."""
+    """Per-row sum |x - y|^p (p > 0) or non-zero count (p == 0) -> float64 device tensor of shape x.shape[:-1]
+    (or (1,)).  `out`: as in row_reduce."""
     torch = _torch()
     x = require(x)
     n = x.shape[-1] if x.ndim > 0 else 1
-    rows = x.numel() // max(n, 1) if x.numel() else 0
+    rows = int(np.prod(x.shape[:-1])) if x.ndim > 1 else 1  # rows of zero elements reduce to 0 (pxa_row_reduce)
     if y is not None:
         y = require(y)
         assert y.shape == x.shape
     if out is None:
         out = torch.empty((max(rows, 1),), dtype=torch.float64, device=x.device)
-    if rows == 0:
-        return out.zero_()
+    else:
+        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == max(rows, 1)
+    if x.numel() == 0:  # no rows, or rows without elements: the statistic of an empty row is 0
+        out.zero_()
+        return out.reshape(x.shape[:-1]) if x.ndim > 1 and rows > 0 else out
     step = 65535
     es = x.element_size()
     for r0 in range(0, rows, step):
@@ -805,7 +810,7 @@ def row_reduce_pow(p, x, y=None, out=None):
         check(lib.pxa_row_reduce_pow(dtcode(x), r1 - r0, n, float(p), ptr(x) + r0 * n * es,
                                      (ptr(y) + r0 * n * es) if y is not None else None, out.data_ptr() + r0 * 8,
                                      ptr(work), stream()), "pxa_row_reduce_pow")
-    return out
+    return out.reshape(x.shape[:-1]) if x.ndim > 1 else out
 
 
 # ------------------------------------------------------------------ stencils

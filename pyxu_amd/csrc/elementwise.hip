@@ -147,6 +147,7 @@ enum GroupMode { kProx = 0, kFenchel = 1, kMoreau = 2, kNorm = 3 };
 template <typename T, int MODE>
 __global__ void __launch_bounds__(kBlock) group_kernel(int64_t outer, int64_t group, int64_t inner,
                                                        const T* x, T* out, T p0, T p1, T p2) {  // out may alias x
+#pragma clang fp contract(off)  // every product rounded, as in group_vec_one: both kernels give the same bits
   const int64_t total = outer * inner;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
@@ -191,6 +192,7 @@ __global__ void __launch_bounds__(kBlock) group_kernel(int64_t outer, int64_t gr
 template <typename T, int MODE, int G>
 __device__ inline void group_vec_one(const T (&v)[G][kVecN<T>], T (&r)[G][kVecN<T>], T (&nv)[kVecN<T>], T p0, T p1,
                                      T p2) {
+#pragma clang fp contract(off)  // with contraction the backend fuses other products here than in group_kernel's loop
 #pragma unroll
   for (int e = 0; e < kVecN<T>; ++e) {
     T s = T(0);

@@ -45,8 +45,8 @@ __device__ inline double ident() {
 
 template <int OP>
 __device__ inline double combine(double a, double b) {
-  if (OP == PXA_RED_MAXABS) return a > b ? a : b;
-  if (OP == PXA_RED_MIN) return (a < b || a != a) ? a : b;  // NaN in either operand wins
+  if (OP == PXA_RED_MAXABS) return (a > b || a != a) ? a : b;  // NaN in either operand wins
+  if (OP == PXA_RED_MIN) return (a < b || a != a) ? a : b;
   if (OP == PXA_RED_MAX) return (a > b || a != a) ? a : b;
   return a + b;
 }
