@@ -232,6 +232,42 @@ int pxa_row_reduce(int dtype, int op, int64_t rows, int64_t n, const void* x, co
 int pxa_row_reduce_pow(int dtype, int64_t rows, int64_t n, double p, const void* x, const void* y, double* out,
                        void* work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Row threshold search and shrink (csrc/threshold.hip).  Per row of x (rows, n), mu* is the root of
+ *     h(mu) = a sum_i max(|x_i| - mu, 0) - b mu - c          (a > 0, b >= 0, c >= 0)
+ * found by Newton's iteration from the left, and the row is clamped or soft-thresholded at mu*:
+ *   LInfinityNorm.prox(x, tau)  (func/norm.py:255-293, brentq)   : (1, 0, tau),   CLAMP
+ *   L1Ball(r).prox              (func/indicator.py:58-69)        : (1, 0, r),     SOFT
+ *   SquaredL1Norm.prox(x, tau)  (func/norm.py:198-212, the sort) : (2 tau, 1, 0), SOFT
+ * mu* = 0 when a ||x||_1 <= c (the reference's brentq raises there); a row holding a NaN or an inf has
+ * mu* = NaN and an all-NaN output row.  mu (rows doubles) and passes (rows int32: the S pass plus the count
+ * passes) are DEVICE arrays.  Counts are integers and sums are double in an order fixed by (rows, n), so mu*
+ * is reproducible bit for bit.  rows <= 65535.
+ * ------------------------------------------------------------------------------------------- */
+#define PXA_SHRINK_CLAMP 0 /* out = sign(x) min(|x|, mu) */
+#define PXA_SHRINK_SOFT 1  /* out = sign(x) max(|x| - mu, 0) */
+
+/* Longest row of the resident path: 32768 float32 / 16384 float64 elements (1024 threads x 8 16-byte vectors). */
+int64_t pxa_row_threshold_resident_max(int dtype);
+
+/* Resident path, n <= pxa_row_threshold_resident_max(dtype): one workgroup per row holds the row in registers,
+ * runs the whole search and writes out (may be NULL: search only; may alias x), mu and passes in one launch. */
+int pxa_row_threshold_prox(int dtype, int mode, int64_t rows, int64_t n, const void* x, double a, double b, double c,
+                           void* out, double* mu, int32_t* passes, void* stream);
+
+/* Streaming path, any n: enqueues `npasses` count passes (a partial launch over pxa_row_reduce's partition plus
+ * a one-wavefront-per-row update launch each) and returns; with `first` != 0 the S pass comes before them and
+ * initialises mu, state and passes.  state (rows int32, DEVICE): 1 once the row's search has ended; workgroups of
+ * such a row return at once, so surplus passes are cheap.  The caller reads state to learn whether to enqueue
+ * more.  `work`: pxa_row_threshold_workspace_bytes(rows, n) bytes, kept between the calls of one search. */
+size_t pxa_row_threshold_workspace_bytes(int64_t rows, int64_t n);
+int pxa_row_threshold_stream(int dtype, int64_t rows, int64_t n, const void* x, double a, double b, double c, int first,
+                             int64_t npasses, double* mu, int32_t* state, int32_t* passes, void* work, void* stream);
+
+/* out = shrink of each row of x at its mu[row] (device doubles); NaN mu gives a NaN row.  out may alias x. */
+int pxa_row_shrink(int dtype, int mode, int64_t rows, int64_t n, const void* x, const double* mu, void* out,
+                   void* stream);
+
 /* CG iteration tail after A p (opt/solver/cg.py:125-153), for `rows` stacked problems of n entries, in
  * three launches: alpha = (T)(rr / <p, A p>), x += alpha p, r -= alpha A p, rr' = ||r||^2,
  * beta = (T)(rr' / rr), p = r + beta p.  rr: this step's ||r||^2 per row (device double); rr_out (device,

@@ -813,6 +813,116 @@ def row_reduce_pow(p, x, y=None, out=None):
     return out.reshape(x.shape[:-1]) if x.ndim > 1 else out
 
 
+# ------------------------------------------------------------------ row threshold search (csrc/threshold.hip)
+SHRINK_CLAMP, SHRINK_SOFT = 0, 1
+THRESHOLD_FIRST_BATCH = 8  # count passes enqueued before the first look at the state words
+THRESHOLD_MAX_PASSES = 256
+_ROW_SLAB = 65535  # grid.y limit
+
+
+def row_threshold_resident_max(x):
+    return int(lib.pxa_row_threshold_resident_max(dtcode(x)))
+
+
+def _threshold_args(x2, a, b, c):
+    x2 = require(x2)
+    if x2.ndim != 2:
+        raise ValueError(f"pyxu_amd: row threshold expects a (rows, n) array, got shape {tuple(x2.shape)}.")
+    a, b, c = float(a), float(b), float(c)
+    if not (a > 0 and b >= 0 and c >= 0 and np.isfinite(a + b + c)):
+        raise ValueError(f"pyxu_amd: row threshold needs finite a > 0, b >= 0, c >= 0 (got {a}, {b}, {c}).")
+    return x2, a, b, c
+
+
+def _threshold_stream(x2, r0, r1, a, b, c, mu, passes, batch):
+    """Streaming search of rows [r0, r1): batches of count passes until every state word is set."""
+    torch = _torch()
+    rows, n, es = r1 - r0, x2.shape[1], x2.element_size()
+    state = torch.empty((rows,), dtype=torch.int32, device=x2.device)
+    wsz = int(lib.pxa_row_threshold_workspace_bytes(rows, n))
+    work = torch.empty((max(wsz // 8, 1),), dtype=torch.float64, device=x2.device)
+    batch = THRESHOLD_FIRST_BATCH if batch is None else int(batch)
+    assert batch >= 1
+    total, first = 0, 1
+    while True:
+        check(lib.pxa_row_threshold_stream(dtcode(x2), rows, n, ptr(x2) + r0 * n * es, a, b, c, first, batch,
+                                           mu.data_ptr() + r0 * 8, state.data_ptr(), passes.data_ptr() + r0 * 4, ptr(work),
+                                           stream()), "pxa_row_threshold_stream")
+        total, first = total + batch, 0
+        if bool(state.cpu().numpy().all()):  # the only host read of a prox
+            return
+        if total >= THRESHOLD_MAX_PASSES:
+            raise RuntimeError("threshold search did not converge")
+        batch = min(batch, THRESHOLD_MAX_PASSES - total)
+
+
+def _threshold_run(x2, a, b, c, mode, out, batch):
+    """(mu, passes, out): the search over every slab of rows and, with `out`, the shrink."""
+    torch = _torch()
+    rows, n = x2.shape
+    mu = torch.zeros((rows,), dtype=torch.float64, device=x2.device)
+    passes = torch.zeros((rows,), dtype=torch.int32, device=x2.device)
+    if rows == 0 or n == 0:
+        return mu, passes, out
+    es = x2.element_size()
+    resident = n <= row_threshold_resident_max(x2)
+    for r0 in range(0, rows, _ROW_SLAB):
+        r1 = min(rows, r0 + _ROW_SLAB)
+        xo, oo = ptr(x2) + r0 * n * es, (ptr(out) + r0 * n * es) if out is not None else None
+        if resident:
+            check(lib.pxa_row_threshold_prox(dtcode(x2), int(mode), r1 - r0, n, xo, a, b, c, oo, mu.data_ptr() + r0 * 8,
+                                             passes.data_ptr() + r0 * 4, stream()), "pxa_row_threshold_prox")
+        else:
+            _threshold_stream(x2, r0, r1, a, b, c, mu, passes, batch)
+            if out is not None:
+                check(lib.pxa_row_shrink(dtcode(x2), int(mode), r1 - r0, n, xo, mu.data_ptr() + r0 * 8, oo, stream()),
+                      "pxa_row_shrink")
+    return mu, passes, out
+
+
+def row_threshold(x2, a, b, c, batch=None):
+    """Per row of x2 (rows, n): the root mu* of a sum max(|x_i| - mu, 0) - b mu - c (0 when a ||x||_1 <= c, NaN for a
+    row that holds a NaN or an inf) -> (mu float64 (rows,), passes int32 (rows,)) on the device.  `batch`: count passes
+    per enqueued batch of the streaming path (long rows); mu* does not depend on it."""
+    x2, a, b, c = _threshold_args(x2, a, b, c)
+    mu, passes, _ = _threshold_run(x2, a, b, c, SHRINK_CLAMP, None, batch)
+    return mu, passes
+
+
+def row_shrink(x2, mu, mode, out=None):
+    """out[r] = sign(x) min(|x|, mu[r]) (SHRINK_CLAMP) or sign(x) max(|x| - mu[r], 0) (SHRINK_SOFT); mu: float64
+    device vector of one threshold per row.  `out` may be x2 itself."""
+    torch = _torch()
+    x2, mu = require(x2), require(mu, "mu")
+    if x2.ndim != 2:
+        raise ValueError(f"pyxu_amd: row_shrink expects a (rows, n) array, got shape {tuple(x2.shape)}.")
+    if mode not in (SHRINK_CLAMP, SHRINK_SOFT):
+        raise ValueError(f"pyxu_amd: unknown shrink mode {mode!r}.")
+    rows, n = x2.shape
+    assert mu.dtype == torch.float64 and mu.numel() == rows
+    out = empty_like(x2) if out is None else out
+    assert out.shape == x2.shape and out.dtype == x2.dtype and out.is_contiguous()
+    es = x2.element_size()
+    for r0 in range(0, rows if n > 0 else 0, _ROW_SLAB):
+        r1 = min(rows, r0 + _ROW_SLAB)
+        check(lib.pxa_row_shrink(dtcode(x2), int(mode), r1 - r0, n, ptr(x2) + r0 * n * es, mu.data_ptr() + r0 * 8,
+                                 ptr(out) + r0 * n * es, stream()), "pxa_row_shrink")
+    return out
+
+
+def row_threshold_prox(x2, a, b, c, mode, out=None, batch=None, info=False):
+    """The threshold search and the shrink at its root: rows of up to row_threshold_resident_max elements in one
+    launch, longer rows by streaming passes and pxa_row_shrink.  `out` may be x2 itself.  `info`: also return
+    (mu, passes)."""
+    x2, a, b, c = _threshold_args(x2, a, b, c)
+    if mode not in (SHRINK_CLAMP, SHRINK_SOFT):
+        raise ValueError(f"pyxu_amd: unknown shrink mode {mode!r}.")
+    out = empty_like(x2) if out is None else out
+    assert out.shape == x2.shape and out.dtype == x2.dtype and out.is_contiguous()
+    mu, passes, out = _threshold_run(x2, a, b, c, mode, out, batch)
+    return (out, mu, passes) if info else out
+
+
 # ------------------------------------------------------------------ stencils
 def stencil_axis(x, y, stack, shape, axis, offsets, coefs, zero_partial=False, xs=None, ys=None, beta=0.0, x_off=0, y_off=0):
     """One separable-axis pass (see pxa_stencil_axis).  `x_off`/`y_off`: element offsets into x/y."""

@@ -47,6 +47,11 @@ EXPORTS = {
     "pxa_row_reduce_workspace_bytes": (sz, [i64, i64]),
     "pxa_row_reduce": (i32, [i32, i32, i64, i64, vp, vp, vp, vp, vp]),
     "pxa_row_reduce_pow": (i32, [i32, i64, i64, f64, vp, vp, vp, vp, vp]),
+    "pxa_row_threshold_resident_max": (i64, [i32]),
+    "pxa_row_threshold_prox": (i32, [i32, i32, i64, i64, vp, f64, f64, f64, vp, vp, vp, vp]),
+    "pxa_row_threshold_workspace_bytes": (sz, [i64, i64]),
+    "pxa_row_threshold_stream": (i32, [i32, i64, i64, vp, f64, f64, f64, i32, i64, vp, vp, vp, vp, vp]),
+    "pxa_row_shrink": (i32, [i32, i32, i64, i64, vp, vp, vp, vp]),
     "pxa_relerr_stats_workspace_bytes": (sz, [i64, i64]),
     "pxa_relerr_stats": (i32, [i32, i64, i64, vp, vp, vp, vp, vp, vp]),
     "pxa_tile_partials_fold": (i32, [i64, i64, vp, vp, vp, ct.c_uint32, vp]),

@@ -40,6 +40,18 @@ struct Vec4<double> {
   using type = double2;  // 16 B per lane for both precisions
 };
 
+// Workgroups per row of the row reductions (reduce.hip) and the streaming threshold search (threshold.hip):
+// workgroup b of a row owns elements [b chunk, (b + 1) chunk), chunk = ceil(n / blocks).  Depends on (rows, n) only.
+inline int blocks_per_row(int64_t rows, int64_t n) {
+  int64_t per = (n + 4095) / 4096;  // >= 4 K elements per workgroup
+  int64_t cap = rows > 0 ? (4096 + rows - 1) / rows : 1;  // ~16 workgroups per CU in total
+  if (cap < 1) cap = 1;
+  if (per > cap) per = cap;
+  if (per > 1024) per = 1024;
+  if (per < 1) per = 1;
+  return (int)per;
+}
+
 // Current value of a pxa_tuning() knob (abi.hip).
 int tuning(int key);
 

@@ -9,16 +9,6 @@
 namespace pxa {
 namespace {
 
-inline int blocks_per_row(int64_t rows, int64_t n) {
-  int64_t per = (n + 4095) / 4096;  // >= 4 K elements per workgroup
-  int64_t cap = rows > 0 ? (4096 + rows - 1) / rows : 1;  // ~16 workgroups per CU in total
-  if (cap < 1) cap = 1;
-  if (per > cap) per = cap;
-  if (per > 1024) per = 1024;
-  if (per < 1) per = 1;
-  return (int)per;
-}
-
 template <typename T, int OP>
 __device__ inline double elem(T x, T y) {
   if (OP == PXA_RED_SUMSQ) return (double)x * (double)x;
