@@ -657,6 +657,37 @@ int pxa_pds_step(int dtype, int algo, const int64_t* geom, const int32_t* ntaps,
 int pxa_tv_dual_update(int dtype, int relax, const int64_t* geom, const double* diff, double sigma, double lam,
                        double rho, int h_kind, const void* w, const void* z, void* z_out, void* stream);
 
+/* Slab form of pxa_pds_step: the same iteration (PD3O.m_step, opt/solver/pds.py:747-761, algo 0; CondatVu.m_step,
+ * pds.py:429-442, algo 1) evaluated on ONE RANK'S SLAB of axis-0 planes of a 3-D volume split over several devices
+ * (the role of the reference's Dask map_overlap, operator/linop/stencil/stencil.py:578-606, for the fused step).
+ * geom is pxa_pds_step's with n0 = nl, the slab's planes, and every state array is compact: x, u, hty, work_q,
+ * work_w (stack, nl, n1, n2), z (stack, D, nl, n1, n2).  The planes the kernels read beyond the slab arrive in ghost
+ * buffers, as received from the neighbours: a "lo" buffer holds the planes just before plane 0 (plane -1 last), a
+ * "hi" buffer the planes just after plane nl - 1 (plane nl first).  A NULL ghost pointer means that side is the
+ * edge of the volume: the zero-boundary rules of pxa_pds_step apply there, and with every ghost NULL the two calls
+ * produce the bits of pxa_pds_step.  A non-NULL ghost asserts that all its planes lie inside the volume.
+ * Two calls per iteration, because the dual update needs w on the first plane of the next slab:
+ *   pxa_pds_slab_primal: kernels A and B; writes x_out, (PD3O) u_out and work_w = w on the slab's planes.
+ *   pxa_pds_slab_dual  : kernel C, z_out = relax(fenchel_prox(z + sigma K w)), with w's first hi plane in w_hi.
+ * ghost = {src_lo, src_hi, z_lo, z_hi} depths in planes (>= the reach below; NULL allowed when every ghost is NULL);
+ *   src_lo / src_hi: (stack, depth, n1, n2) planes of u (PD3O) or x (CV); read when axis 0 is blurred, reach 2 R0
+ *                    per side (R0 = max |offset| of the axis-0 taps);
+ *   z_lo: PD3O (stack, D, depth, n1, n2), reach 2 R0 + 1; CV (stack, depth, n1, n2) = direction 0 only, reach 1;
+ *   z_hi: PD3O (stack, D, depth, n1, n2), reach 2 R0, read when axis 0 is blurred; CV: never read.
+ * The ghosts a side needs are all given or all NULL.  Errors (PXA_ERR_ARG, nothing launched): n0 = 1 / D = 2 images;
+ * ghosts with D = 2 (batch-as-axis volumes differentiate axes 1, 2 only and need none); a depth below the reach; a
+ * ghost aliasing an output.  u_out may alias u.  Neither call allocates or synchronises.
+ * pxa_pds_slab_dual: arguments as pxa_tv_dual_update (geom = {stack, nl, n1, n2, D}) plus w_hi (stack, w_hi_depth,
+ *   n1, n2), w_hi_depth >= 1, or NULL at the volume's last slab; z_out may alias z. */
+int pxa_pds_slab_primal(int dtype, int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs,
+                        const double* coefs, const double* diff, const double* scal, int prox, int h_kind,
+                        const void* x, const void* u, const void* z, const void* hty, void* x_out, void* u_out,
+                        void* work_q, void* work_w, const int64_t* ghost, const void* src_lo, const void* src_hi,
+                        const void* z_lo, const void* z_hi, int nseg, void* stream);
+int pxa_pds_slab_dual(int dtype, int relax, const int64_t* geom, const double* diff, double sigma, double lam,
+                      double rho, int h_kind, const void* w, const void* w_hi, int64_t w_hi_depth, const void* z,
+                      void* z_out, void* stream);
+
 /* Look-ahead form of pxa_pds_step (same problem class and arguments, pds_march.hpp): two launches per
  * iteration, kernel B and kernel D = the dual update of this iteration fused with the axis-0 march of
  * the next one, which is therefore already done when the next call starts (primed = 1).  A call with

@@ -1245,6 +1245,86 @@ def pds_step_la(algo, pre, primed, x, u, z, hty, x_out, u_out, z_out, work_q, wo
         _TIMER.end(ev)
 
 
+def _slab_operand(t, name, like, numel=None):
+    """A state or ghost array of the slab step: device tensor of `like`'s dtype, contiguous (never copied: the kernels
+    write into / read from exactly this buffer), optionally of `numel` elements."""
+    if t is None:
+        return None
+    if not (hasattr(t, "is_cuda") and t.is_cuda):
+        raise TypeError(f"pyxu_amd: `{name}` must be an MI355X device tensor")
+    if t.dtype != like.dtype:
+        raise TypeError(f"pyxu_amd: `{name}` has dtype {t.dtype}, the state has {like.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"pyxu_amd: `{name}` must be contiguous")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"pyxu_amd: `{name}` holds {t.numel()} elements, the slab geometry needs {numel}")
+    return t
+
+
+def _ghost_depth(t, name, like, per_plane):
+    """Depth in planes of a ghost buffer whose planes hold `per_plane` elements each (0 for None)."""
+    if _slab_operand(t, name, like) is None:
+        return 0
+    d, rem = divmod(t.numel(), per_plane)
+    if rem or d < 1:
+        raise ValueError(f"pyxu_amd: ghost `{name}` of {t.numel()} elements is not a whole number of planes "
+                         f"({per_plane} elements each)")
+    return d
+
+
+def pds_slab_primal(algo, pre, x, u, z, hty, x_out, u_out, work_q, work_w, src_lo=None, src_hi=None, z_lo=None,
+                    z_hi=None, nseg=0):
+    """Primal part (kernels A and B) of the fused PD3O (algo 0) / Condat-Vu (algo 1) iteration on one rank's slab of
+    axis-0 planes (pxa_pds_slab_primal); `pre` from pds_args with n0 = the slab's planes.  Ghost buffers hold the
+    neighbours' planes, (stack, depth, n1, n2) for src (u / x) and for Condat-Vu's z_lo (direction 0), (stack, D,
+    depth, n1, n2) for PD3O's z; None = the volume's edge.  Writes x_out, u_out (PD3O) and work_w."""
+    stack, y_images, n0, n1, n2, D = (int(v) for v in pre[0])
+    Mp, N = n1 * n2, n0 * n1 * n2
+    z = _slab_operand(z, "z", z, stack * D * N)
+    _slab_operand(hty, "hty", z, y_images * N)
+    for name, t in (("x", x), ("u", u), ("x_out", x_out), ("u_out", u_out), ("work_q", work_q), ("work_w", work_w)):
+        _slab_operand(t, name, z, stack * N)
+    zdirs = D if algo == 0 else 1
+    depths = [_ghost_depth(src_lo, "src_lo", z, stack * Mp), _ghost_depth(src_hi, "src_hi", z, stack * Mp),
+              _ghost_depth(z_lo, "z_lo", z, stack * zdirs * Mp), _ghost_depth(z_hi, "z_hi", z, stack * zdirs * Mp)]
+    outs = [t.data_ptr() for t in (x_out, u_out, work_q, work_w) if t is not None]
+    for name, t in (("src_lo", src_lo), ("src_hi", src_hi), ("z_lo", z_lo), ("z_hi", z_hi)):
+        if t is not None and t.data_ptr() in outs:
+            raise ValueError(f"pyxu_amd: ghost `{name}` aliases an output of the step")
+    if algo == 1 and x_out is not None and x is not None and x_out.data_ptr() == x.data_ptr():
+        raise ValueError("pyxu_amd: Condat-Vu's x_out must not alias x")
+    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    ev = _TIMER.begin() if _TIMER is not None else None
+    check(lib.pxa_pds_slab_primal(dtcode(z), int(algo), *pre, p(x), p(u), p(z), p(hty), p(x_out), p(u_out), p(work_q),
+                                  p(work_w), i64_array(depths), p(src_lo), p(src_hi), p(z_lo), p(z_hi), int(nseg),
+                                  stream()), "pxa_pds_slab_primal")
+    if ev is not None:
+        _TIMER.end(ev)
+
+
+def pds_slab_dual(w, z, geom, c0, c1, sigma, lam, rho, h_kind, relax=0, w_hi=None, out=None):
+    """Dual part (kernel C) of the slab step, and the ghost-aware form of tv_dual_update (pxa_pds_slab_dual):
+    z_out = relax(fenchel_prox_{sigma h}(z + sigma Grad w)) on one rank's slab; w_hi = the first plane(s) of the next
+    slab's w as (stack, depth, n1, n2), None at the volume's last slab.  geom = (stack, nl, n1, n2, D)."""
+    stack, n0, n1, n2, D = (int(v) for v in geom)
+    N = n0 * n1 * n2
+    z = _slab_operand(z, "z", z, stack * D * N)
+    _slab_operand(w, "w", z, stack * N)
+    depth = _ghost_depth(w_hi, "w_hi", z, stack * n1 * n2)
+    out = empty_like(z) if out is None else _slab_operand(out, "out", z, z.numel())
+    for name, t in (("w", w), ("w_hi", w_hi)):
+        if t is not None and t.data_ptr() == out.data_ptr():
+            raise ValueError(f"pyxu_amd: `{name}` aliases the output of the dual update")
+    ev = _TIMER.begin() if _TIMER is not None else None
+    check(lib.pxa_pds_slab_dual(dtcode(z), int(relax), i64_array([stack, n0, n1, n2, D]),
+                                f64_array(list(c0) + list(c1)), float(sigma), float(lam), float(rho), int(h_kind),
+                                ptr(w), None if w_hi is None else ptr(w_hi), depth, ptr(z), ptr(out), stream()),
+          "pxa_pds_slab_dual")
+    if ev is not None:
+        _TIMER.end(ev)
+    return out
+
+
 def tv_dual_update(w, z, geom, c0, c1, sigma, lam, rho, h_kind, relax=0, out=None):
     """z_out = relax(fenchel_prox_{sigma h}(z + sigma Grad w)), h = lam L1 (h_kind 0) / lam L21 (1):
     the PDS dual update alone (pxa_tv_dual_update).  geom = (stack, n0, n1, n2, D); relax 0 PD3O, 1 CV."""

@@ -30,6 +30,13 @@
 //    equals (pds3d.hpp dual_out), and the relaxation.
 //  * pxa_pds_step_la replaces kernels C and A by kernel D (pds_march.hpp): the dual update of iteration k
 //    fused with the axis-0 march of iteration k + 1, two launches per iteration.
+//  * pxa_pds_slab_primal (kernels A, B) + pxa_pds_slab_dual (kernel C) evaluate the three-launch step on one
+//    rank's slab of axis-0 planes of a volume split over several devices: the state arrays are the compact slab,
+//    the planes beyond it (2 R0 per side for the march, one lo plane of z_0, one hi plane of w) are read from
+//    ghost buffers filled by the neighbours, a null ghost is the volume's edge.  The plane index of kernels A and
+//    C is uniform per march step, so ghost or owned is a choice of base pointer; the ghost-aware forms are
+//    separate instantiations (GhostA / PdsPtrsSlab / GhostC; pds_slab_f32.hip, pds_slab_f64.hip), and the
+//    unsharded launches keep their code.  Same expressions per voxel: the bits of pxa_pds_step.
 // Compulsory HBM traffic per voxel (fp32): PD3O A 24 B + B 24 B + C 28 B = 76 B (80 B);
 // Condat-Vu A 8 B + B 32 B + C 28 B = 68 B (SURVEY: 68 B).
 //
@@ -90,9 +97,19 @@ __device__ inline void ldv(const T* p, T (&v)[NV]) {
 // PF (the default; PXA_TUNE_DUAL_ROWS = 1 turns it off): z and the row + 1 / column + 1 neighbours of plane p + 1 are
 // loaded while plane p is computed (two planes of loads in flight per thread); the same values in the same expressions:
 // the same bits.
-template <typename T, int NV, bool ISO, bool PD3O, bool NT, bool PF = false>
+// GH = GhostC<T> (pxa_pds_slab_dual): the n0 planes are one rank's slab, and w at plane n0 is plane 0 of w_hi, the
+// next slab's first planes as (stack, dhi, n1, n2); null: the volume's edge.  The plane index is uniform over the
+// workgroup: a choice of base pointer.
+template <typename T>
+struct GhostC {
+  const T* w_hi;
+  int64_t dhi;
+};
+
+template <typename T, int NV, bool ISO, bool PD3O, bool NT, bool PF = false, typename GH = NoGhost>
 __global__ void __launch_bounds__(kBlock) pds_dual_kernel(PdsC<T> p, const T* __restrict__ w,
-                                                          const T* __restrict__ z, T* __restrict__ zo) {
+                                                          const T* __restrict__ z, T* __restrict__ zo, GH gh = GH()) {
+  constexpr bool SLAB = !std::is_same<GH, NoGhost>::value;
   const PdsGeom<T> g = p.g;
   const T sigma = p.sigma, lam = p.lam, rho = p.rho, omr = p.omr;
   const int n0 = g.n0, n1 = g.n1, n2 = g.n2, D = g.D;
@@ -137,8 +154,12 @@ __global__ void __launch_bounds__(kBlock) pds_dual_kernel(PdsC<T> p, const T* __
     T wc[NV], wp[NV];
 #pragma unroll
     for (int e = 0; e < NV; ++e) wc[e] = wn0[e];
+    bool ghost = false;
+    if constexpr (SLAB) ghost = pl + 1 == n0 && gh.w_hi != nullptr;
     if (pl + 1 < n0) {
       ldv<T, NV>(ws + off + M, wp);
+    } else if (ghost) {
+      if constexpr (SLAB) ldv<T, NV>(gh.w_hi + s * gh.dhi * M + j0, wp);
     } else {
 #pragma unroll
       for (int e = 0; e < NV; ++e) wp[e] = T(0);
@@ -540,9 +561,24 @@ int launch_c(const PdsC<T>& pc, bool iso, int64_t M, int nseg, const void* w, co
 // Kernel C over a whole (stack, n0, n1, n2) geometry: z_out = relax(fenchel_prox_h(z + sigma K w)).  The
 // march is split into axis-0 segments so that about 2048 workgroups are in flight (no halo: w(p + 1) is a
 // plain load; at 1024^3 2048 took 5.0-5.1 ms against 5.1-5.7 ms at 4096, profiles/r04_k4_wgs.txt).  pd3o selects the relaxation order: (1 - rho) z + rho z_t, else rho z_t + (1 - rho) z.
+// Slab form: always the one-row kernel with the next plane's loads one plane early (launch_c's default).
+template <typename T, int NV, bool PD3O>
+int launch_c_slab(const PdsC<T>& pc, bool iso, int64_t M, int nseg, const void* w, const void* z, void* zo,
+                  const GhostC<T>& gh, hipStream_t st) {
+  const int64_t blocks = (M + (int64_t)kBlock * NV - 1) / ((int64_t)kBlock * NV);
+  dim3 grid((unsigned)blocks, (unsigned)nseg, (unsigned)pc.g.stack);
+  if (iso)
+    hipLaunchKernelGGL((pds_dual_kernel<T, NV, true, PD3O, true, true, GhostC<T>>), grid, dim3(kBlock), 0, st, pc,
+                       (const T*)w, (const T*)z, (T*)zo, gh);
+  else
+    hipLaunchKernelGGL((pds_dual_kernel<T, NV, false, PD3O, true, true, GhostC<T>>), grid, dim3(kBlock), 0, st, pc,
+                       (const T*)w, (const T*)z, (T*)zo, gh);
+  return last_launch_status();
+}
+
 template <typename T>
 int run_c(const PdsGeom<T>& g, T sigma, T lam, T rho, T omr, bool pd3o, bool iso, const void* w, const void* z,
-          void* z_out, hipStream_t st) {
+          void* z_out, hipStream_t st, const GhostC<T>* gh = nullptr) {
   constexpr int V = kVecN<T>;
   const int64_t M = (int64_t)g.n1 * g.n2;
   PdsC<T> pc;
@@ -551,9 +587,9 @@ int run_c(const PdsGeom<T>& g, T sigma, T lam, T rho, T omr, bool pd3o, bool iso
   pc.lam = lam;
   pc.rho = rho;
   pc.omr = omr;
-  const bool vec = (g.n2 % V == 0) && aligned16(w) && aligned16(z) && aligned16(z_out);
+  const bool vec = (g.n2 % V == 0) && aligned16(w) && aligned16(z) && aligned16(z_out) && (!gh || aligned16(gh->w_hi));
   const int nv = vec ? V : 1;
-  const int64_t rbt = tuning(PXA_TUNE_DUAL_ROWS);
+  const int64_t rbt = gh ? 0 : tuning(PXA_TUNE_DUAL_ROWS);
   const int64_t rbk = rbt == 2 ? 2 : rbt == 4 ? 4 : 1;
   int64_t blocks = g.stack * ((M + (int64_t)kBlock * nv * rbk - 1) / ((int64_t)kBlock * nv * rbk));
   if ((rbt == 8 || rbt == 9) && vec && g.D == 3 && sizeof(T) == 4)  // (the plane-block kernel's block count)
@@ -564,6 +600,13 @@ int run_c(const PdsGeom<T>& g, T sigma, T lam, T rho, T omr, bool pd3o, bool iso
   if (cseg < 1) cseg = 1;
   pc.seg = (int)((g.n0 + cseg - 1) / cseg);
   cseg = (int)((g.n0 + pc.seg - 1) / pc.seg);
+  if (gh) {
+    if (vec)
+      return pd3o ? launch_c_slab<T, V, true>(pc, iso, M, cseg, w, z, z_out, *gh, st)
+                  : launch_c_slab<T, V, false>(pc, iso, M, cseg, w, z, z_out, *gh, st);
+    return pd3o ? launch_c_slab<T, 1, true>(pc, iso, M, cseg, w, z, z_out, *gh, st)
+                : launch_c_slab<T, 1, false>(pc, iso, M, cseg, w, z, z_out, *gh, st);
+  }
   if (vec)
     return pd3o ? launch_c<T, V, true>(pc, iso, M, cseg, w, z, z_out, st) : launch_c<T, V, false>(pc, iso, M, cseg, w, z, z_out, st);
   return pd3o ? launch_c<T, 1, true>(pc, iso, M, cseg, w, z, z_out, st) : launch_c<T, 1, false>(pc, iso, M, cseg, w, z, z_out, st);
@@ -712,7 +755,7 @@ PdsA<T> make_a(const PdsSetup<T>& S, int& nseg) {
 // kernel B: mode 0 PD3O, 1 Condat-Vu (K^T z from z), 2 Condat-Vu (K^T z given in `z`)
 template <typename T>
 int stage_b(const PdsSetup<T>& S, int mode, const void* q_src, const void* xin, const void* u, const void* z,
-            const void* hty, void* w, void* out, hipStream_t st) {
+            const void* hty, void* w, void* out, hipStream_t st, const PdsPtrsSlab* slab = nullptr) {
   constexpr int V = kVecN<T>;
   const int R = S.R;
   PdsB<T> pb;
@@ -746,6 +789,11 @@ int stage_b(const PdsSetup<T>& S, int mode, const void* q_src, const void* xin, 
   pb.vec_ok = (S.g.n2 % V == 0) && aligned16(q_src) && aligned16(xin) && aligned16(hty) && aligned16(w) &&
               aligned16(out) && aligned16(z) && (mode != 0 || aligned16(u));
   PdsPtrs P{q_src, xin, u, z, hty, w, out};
+  if (slab) {  // mode 1 on a slab: the z_0 ghost plane
+    pb.vec_ok = pb.vec_ok && aligned16(slab->z_lo);
+    PdsPtrsSlab PS{P, slab->z_lo, slab->z_dlo};
+    return run_b_slab(pb, R, PS, st);
+  }
   return run_b(pb, mode, R, P, st);
 }
 
@@ -793,6 +841,109 @@ int pds_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int32_t
   if (const int e = run_c<T>(g, S.sigma, S.lam, S.rho, S.omr, pd3o, S.iso, work_w, z, z_out, st)) return e;
   if (evs) pds_event(3, st);
   return PXA_OK;
+}
+
+// pxa_pds_slab_dual: kernel C on one rank's slab, w at plane nl from the next slab (w_hi; null: the volume's edge)
+template <typename T>
+int dual_slab_entry(int relax, const int64_t* geom, const double* diff, double sigma, double lam, double rho,
+                    int h_kind, const void* w, const void* w_hi, int64_t w_hi_depth, const void* z, void* z_out,
+                    hipStream_t st) {
+  PXA_CHECK_ARG(geom && diff && w && z && z_out && z_out != w);
+  PXA_CHECK_ARG(relax == 0 || relax == 1);
+  PXA_CHECK_ARG(h_kind == 0 || h_kind == 1);
+  const int64_t stack = geom[0], n0 = geom[1], n1 = geom[2], n2 = geom[3], D = geom[4];
+  PXA_CHECK_ARG(stack >= 1 && stack <= 65535 && n0 >= 1 && n1 >= 1 && n2 >= 1);
+  PXA_CHECK_ARG(n0 <= 0x7fffffff && n1 <= 0x7fffffff && n2 <= 0x7fffffff && n0 * n1 * n2 <= ((int64_t)1 << 40));
+  PXA_CHECK_ARG(D == 3 || (D == 2 && n0 > 1));  // volumes only: an image has no axis-0 neighbour
+  PXA_CHECK_ARG(w_hi_depth >= 0 && w_hi_depth <= 0x7fffffff);
+  if (w_hi != nullptr) {
+    PXA_CHECK_ARG(D == 3);             // axis 0 not differentiated: no ghost is read
+    PXA_CHECK_ARG(w_hi_depth >= 1);    // kernel C reads one plane ahead
+    PXA_CHECK_ARG(w_hi != z_out);
+  }
+  PdsGeom<T> g;
+  g.stack = stack;
+  g.y_images = 1;
+  g.n0 = (int)n0;
+  g.n1 = (int)n1;
+  g.n2 = (int)n2;
+  g.D = (int)D;
+  for (int a = 0; a < 3; ++a) {
+    g.c0[a] = (T)diff[a];
+    g.c1[a] = (T)diff[3 + a];
+  }
+  const GhostC<T> gh{(const T*)w_hi, w_hi != nullptr ? w_hi_depth : 0};
+  return run_c<T>(g, (T)sigma, (T)lam, (T)rho, (T)(1.0 - rho), relax == 0, h_kind == 1, w, z, z_out, st, &gh);
+}
+
+// pxa_pds_slab_primal: kernels A and B of pds_entry on one rank's slab.  ghost = {src_lo, src_hi, z_lo, z_hi}
+// depths; src = u (PD3O) or x (Condat-Vu).  What the kernels read beyond the slab (R0 = axis-0 reach):
+//   PD3O: kernel A builds v on planes [-2 R0, nl + 2 R0): u and z on 2 R0 planes per side, and z_0 on one more lo
+//         plane (the backward neighbour of K^T z at the first plane of the march); kernel B nothing.
+//   CV  : kernel A x on 2 R0 planes per side; kernel B z_0 on one lo plane (z_lo holds direction 0 only).
+template <typename T>
+int pds_slab_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs, const double* coefs,
+                   const double* diff, const double* scal, int prox, int h_kind, const void* x, const void* u,
+                   const void* z, const void* hty, void* x_out, void* u_out, void* work_q, void* work_w,
+                   const int64_t* ghost, const void* src_lo, const void* src_hi, const void* z_lo, const void* z_hi,
+                   int nseg, hipStream_t st) {
+  PXA_CHECK_ARG(algo == 0 || algo == 1);
+  PdsSetup<T> S;
+  if (const int e = pds_setup<T>(geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
+  const bool pd3o = algo == 0;
+  PXA_CHECK_ARG(z && hty && work_w && x_out && (pd3o ? (u && u_out) : (x != nullptr)));
+  PXA_CHECK_ARG(pd3o || x_out != x);
+  if (!S.id0) PXA_CHECK_ARG(work_q != nullptr);
+  const PdsGeom<T>& g = S.g;
+  PXA_CHECK_ARG(g.n0 > 1 || g.D == 3);  // volumes only (n0 = 1 / D = 2 images have no axis-0 neighbour)
+  const bool any = src_lo || src_hi || z_lo || z_hi;
+  PXA_CHECK_ARG(ghost != nullptr || !any);
+  int64_t d[4] = {0, 0, 0, 0};
+  if (ghost)
+    for (int i = 0; i < 4; ++i) {
+      PXA_CHECK_ARG(ghost[i] >= 0 && ghost[i] <= 0x7fffffff);
+      d[i] = ghost[i];
+    }
+  if (any) PXA_CHECK_ARG(g.D == 3);  // the batch-as-axis form (directions (1, 2)) needs no ghosts
+  const int R2 = 2 * S.R0;
+  // a side is either the volume's edge (no ghost) or has every ghost its kernels read, deep enough
+  const bool need_src = S.R0 > 0, need_zhi = pd3o && S.R0 > 0;
+  const bool lo = z_lo != nullptr, hi = need_src ? src_hi != nullptr : (z_hi != nullptr || src_hi != nullptr);
+  if (need_src) PXA_CHECK_ARG((src_lo != nullptr) == lo);
+  if (need_zhi) PXA_CHECK_ARG((z_hi != nullptr) == hi);
+  if (lo) PXA_CHECK_ARG(d[2] >= (pd3o ? R2 + 1 : 1) && (!need_src || d[0] >= R2));
+  if (hi) PXA_CHECK_ARG((!need_src || d[1] >= R2) && (!need_zhi || d[3] >= R2));
+  const void* ghosts[4] = {src_lo, src_hi, z_lo, z_hi};
+  for (const void* gp : ghosts)
+    if (gp) PXA_CHECK_ARG(gp != x_out && gp != u_out && gp != work_q && gp != work_w);
+  const int64_t M = S.M;
+
+  // ---- kernel A
+  const void* q_src = pd3o ? (const void*)x_out : x;
+  if (pd3o || !S.id0) {
+    const PdsA<T> pa = make_a(S, nseg);
+    const void* src = pd3o ? u : x;
+    auto a2 = [](const void* p) { return (uintptr_t)p % (2 * sizeof(T)) == 0; };
+    const bool np2 = (g.n2 % 2 == 0) && a2(src) && a2(z) && a2(x_out) && (S.id0 || a2(work_q)) && a2(src_lo) &&
+                     a2(src_hi) && a2(z_lo) && a2(z_hi);
+    GhostA<T> gh;
+    gh.src_lo = need_src && lo ? (const T*)src_lo : nullptr;
+    gh.src_hi = need_src && hi ? (const T*)src_hi : nullptr;
+    gh.z_lo = pd3o && lo ? (const T*)z_lo : nullptr;
+    gh.z_hi = need_zhi && hi ? (const T*)z_hi : nullptr;
+    gh.src_dlo = (int)d[0];
+    gh.src_dhi = (int)d[1];
+    gh.z_dlo = (int)d[2];
+    gh.z_dhi = (int)d[3];
+    void* q = S.id0 ? x_out : work_q;  // R0 == 0 never writes q
+    const int e = run_a_slab(pa, gh, pd3o, S.R0, np2 ? 2 : 1, M, nseg, src, z, x_out, q, st);
+    if (e) return e;
+    if (!S.id0) q_src = work_q;
+  }
+  // ---- kernel B
+  if (pd3o) return stage_b(S, 0, q_src, x_out, u, z, hty, work_w, u_out, st);
+  const PdsPtrsSlab zl{{}, lo ? z_lo : nullptr, lo ? d[2] : 0};
+  return stage_b(S, 1, q_src, x, u, z, hty, work_w, x_out, st, &zl);
 }
 
 // Look-ahead step (pds_march.hpp): [priming march] + kernel B + kernel D.  PD3O: x (current x; written by
@@ -889,6 +1040,25 @@ int pxa_tv_dual_update(int dtype, int relax, const int64_t* geom, const double* 
                        double rho, int h_kind, const void* w, const void* z, void* z_out, void* stream) {
   PXA_DISPATCH(dtype, T,
                return dual_entry<T>(relax, geom, diff, sigma, lam, rho, h_kind, w, z, z_out, as_stream(stream)));
+}
+
+int pxa_pds_slab_primal(int dtype, int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs,
+                        const double* coefs, const double* diff, const double* scal, int prox, int h_kind,
+                        const void* x, const void* u, const void* z, const void* hty, void* x_out, void* u_out,
+                        void* work_q, void* work_w, const int64_t* ghost, const void* src_lo, const void* src_hi,
+                        const void* z_lo, const void* z_hi, int nseg, void* stream) {
+  PXA_DISPATCH(dtype, T,
+               return pds_slab_entry<T>(algo, geom, ntaps, offs, coefs, diff, scal, prox, h_kind, x, u, z, hty, x_out,
+                                        u_out, work_q, work_w, ghost, src_lo, src_hi, z_lo, z_hi, nseg,
+                                        as_stream(stream)));
+}
+
+int pxa_pds_slab_dual(int dtype, int relax, const int64_t* geom, const double* diff, double sigma, double lam,
+                      double rho, int h_kind, const void* w, const void* w_hi, int64_t w_hi_depth, const void* z,
+                      void* z_out, void* stream) {
+  PXA_DISPATCH(dtype, T,
+               return dual_slab_entry<T>(relax, geom, diff, sigma, lam, rho, h_kind, w, w_hi, w_hi_depth, z, z_out,
+                                         as_stream(stream)));
 }
 
 int pxa_pds_step_la(int dtype, int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs,

@@ -142,14 +142,29 @@ struct PdsA {
   int seg;  // planes per segment (grid.y splits axis 0 into segments)
 };
 
+// Ghost planes of a slab (pxa_pds_slab_primal): the n0 planes of the geometry are one rank's slab of axis-0
+// planes of a larger volume, and the planes the march reads beyond them come from the neighbours' slabs:
+// lo buffers hold the planes just before plane 0 (plane -1 last), hi buffers the planes just after plane
+// n0 - 1 (plane n0 first).  src_* is (stack, depth, n1, n2), z_* is (stack, D, depth, n1, n2).  A null pointer is
+// the edge of the volume (zero boundary, as without ghosts); a non-null one covers every plane the march reads.
+template <typename T>
+struct GhostA {
+  const T *src_lo, *src_hi, *z_lo, *z_hi;
+  int src_dlo, src_dhi, z_dlo, z_dhi;  // depths in planes
+};
+struct NoGhost {};  // the unsharded launches: no ghost code is generated
+
 // Thread = NP consecutive in-plane positions of one volume; it walks planes [pb - 2 R0, pe + 2 R0)
 // and outputs Q = G0 v on planes [pb, pe) (R0 > 0).  v = x (Condat-Vu) or prox_g(u - tau K^T z) (PD3O,
-// stored to xo on [pb, pe)).
-template <typename T, int R0, int NP, bool PD3O>
+// stored to xo on [pb, pe)).  GH = GhostA<T>: planes outside [0, n0) are read from the ghost buffers; the
+// plane index is uniform over the workgroup, so the choice between ghost and owned planes is a choice of
+// base pointer per plane.
+template <typename T, int R0, int NP, bool PD3O, typename GH = NoGhost>
 __global__ void __launch_bounds__(kAThreads) pds_axis0_kernel(PdsA<T> p, const T* __restrict__ src,
                                                               const T* __restrict__ z, T* __restrict__ xo,
-                                                              T* __restrict__ q) {
+                                                              T* __restrict__ q, GH gh = GH()) {
   constexpr int RING = 2 * R0 + 1;
+  constexpr bool SLAB = !std::is_same<GH, NoGhost>::value;
   // kernel arguments are copied to registers: the lambdas below capture by reference, and taking the
   // address of a kernel argument would move the whole parameter block to scratch memory
   const PdsGeom<T> g = p.g;
@@ -178,8 +193,16 @@ __global__ void __launch_bounds__(kAThreads) pds_axis0_kernel(PdsA<T> p, const T
 #pragma unroll
   for (int k = 0; k < NP; ++k) zp0[k] = T(0);
   if (PD3O && g.D == 3 && pb - 2 * R0 - 1 >= 0) ldn<T, NP>(zs + (int64_t)(pb - 2 * R0 - 1) * M, zp0);
+  // first and one-past-last plane of the volume in slab coordinates (a ghost side has no edge within reach)
+  int vlo = 0, vhi = g.n0;
+  if constexpr (SLAB) {
+    if (PD3O && g.D == 3 && pb - 2 * R0 - 1 < 0 && gh.z_lo != nullptr)
+      ldn<T, NP>(gh.z_lo + (s * g.D * gh.z_dlo + (pb - 2 * R0 - 1 + gh.z_dlo)) * M + j0, zp0);
+    if ((PD3O ? gh.z_lo : gh.src_lo) != nullptr) vlo = -(1 << 30);
+    if ((PD3O ? gh.z_hi : gh.src_hi) != nullptr) vhi = 1 << 30;
+  }
 
-  // v at plane qp (qp inside [0, n0)), returned by value (a reference into the ring would keep the
+  // v at plane qp (qp inside the volume), returned by value (a reference into the ring would keep the
   // ring in scratch memory)
   struct VN {
     T v[NP];
@@ -188,15 +211,34 @@ __global__ void __launch_bounds__(kAThreads) pds_axis0_kernel(PdsA<T> p, const T
     VN r;
     T(&v)[NP] = r.v;
     const int64_t off = (int64_t)qp * M;
+    // SLAB: the plane's input and direction-0 z pointers and the direction stride of z, owned or ghost
+    // (uniform); the unsharded form keeps its own address expressions below
+    const T* inq = nullptr;
+    const T* zq = nullptr;
+    int64_t zN = 0;
+    if constexpr (SLAB) {
+      inq = in + off;
+      zq = zs + off;
+      zN = N;
+      if (qp < 0) {
+        inq = gh.src_lo + (s * gh.src_dlo + (qp + gh.src_dlo)) * M + j0;
+        zN = (int64_t)gh.z_dlo * M;
+        zq = gh.z_lo + s * g.D * zN + (int64_t)(qp + gh.z_dlo) * M + j0;
+      } else if (qp >= g.n0) {
+        inq = gh.src_hi + (s * gh.src_dhi + (qp - g.n0)) * M + j0;
+        zN = (int64_t)gh.z_dhi * M;
+        zq = gh.z_hi + s * g.D * zN + (int64_t)(qp - g.n0) * M + j0;
+      }
+    }
     if constexpr (!PD3O) {
-      ldn<T, NP>(in + off, v);
+      ldn<T, NP>(SLAB ? inq : in + off, v);
     } else {
       T u[NP], kt[NP];
-      ldn<T, NP>(in + off, u);
+      ldn<T, NP>(SLAB ? inq : in + off, u);
 #pragma unroll
       for (int a = 0; a < 3; ++a) {
         if (a < a_first) continue;
-        const T* zd = zs + (int64_t)(a - a_first) * N + off;
+        const T* zd = SLAB ? zq + (int64_t)(a - a_first) * zN : zs + (int64_t)(a - a_first) * N + off;
         T zc[NP], zm[NP];
         ldn<T, NP>(zd, zc);
         if (a == 0) {
@@ -246,7 +288,7 @@ __global__ void __launch_bounds__(kAThreads) pds_axis0_kernel(PdsA<T> p, const T
         constexpr int j = decltype(J)::value;
         const int qp = base + j;
         if (qp > last) return;
-        if (qp >= 0 && qp < g.n0) {
+        if (SLAB ? (qp >= vlo && qp < vhi) : (qp >= 0 && qp < g.n0)) {
           const VN r = load_v(qp);
 #pragma unroll
           for (int k = 0; k < NP; ++k) rv[j][k] = r.v[k];
@@ -254,10 +296,10 @@ __global__ void __launch_bounds__(kAThreads) pds_axis0_kernel(PdsA<T> p, const T
 #pragma unroll
           for (int k = 0; k < NP; ++k) rv[j][k] = T(0);
         }
-        // (H0 v)[qp - R0] = sum_t k0[t] v[qp - 2 R0 + t]; zero outside [0, n0) (Trim o S o Pad)
+        // (H0 v)[qp - R0] = sum_t k0[t] v[qp - 2 R0 + t]; zero outside the volume (Trim o S o Pad)
         const int ph = qp - R0;
         constexpr int jh = (j - R0 + RING) % RING;
-        if (ph >= 0 && ph < g.n0) {
+        if (SLAB ? (ph >= vlo && ph < vhi) : (ph >= 0 && ph < g.n0)) {
           T acc[NP];
 #pragma unroll
           for (int k = 0; k < NP; ++k) acc[k] = T(0);
@@ -314,11 +356,18 @@ struct PdsPtrs {
   void* w;          // w (input of K in the dual update)
   void* out;        // PD3O: u_new ; Condat-Vu: x_new
 };
+// Slab form of MODE 1 (pxa_pds_slab_primal): the axis-0 backward neighbour of K^T z at plane 0 is the last
+// plane of z_lo, direction 0 of the previous slab's z as (stack, z_dlo, n1, n2); null: the volume's edge.
+struct PdsPtrsSlab : PdsPtrs {
+  const void* z_lo;
+  int64_t z_dlo;
+};
 
 // MODE: 0 PD3O; 1 Condat-Vu with K^T z gathered from z; 2 Condat-Vu with K^T z precomputed (kernel D)
-template <typename T, int R, bool EDGE, int MODE>
-__device__ inline void pds_tile(const PdsB<T>& p, const PdsPtrs& P, unsigned char* smem, int64_t img, int ty0,
+template <typename T, int R, bool EDGE, int MODE, typename PP = PdsPtrs>
+__device__ inline void pds_tile(const PdsB<T>& p, const PP& P, unsigned char* smem, int64_t img, int ty0,
                                 int tx0) {
+  constexpr bool SLAB = std::is_same<PP, PdsPtrsSlab>::value;
   using L = Layout<T, R>;
   constexpr int V = L::V;
   constexpr int CA = L::CA;
@@ -487,8 +536,12 @@ __device__ inline void pds_tile(const PdsB<T>& p, const PdsPtrs& P, unsigned cha
         T zc[V], zm[V];
         ld(P.z, zo, zc);
         if (ax == 0) {
+          bool ghost = false;
+          if constexpr (SLAB) ghost = plane == 0 && P.z_lo != nullptr;  // (uniform over the workgroup)
           if (plane > 0) {
             ld(P.z, zo - M, zm);
+          } else if (ghost) {
+            if constexpr (SLAB) ld(P.z_lo, (s * P.z_dlo + (P.z_dlo - 1)) * M + (int64_t)gr * n2 + gc, zm);
           } else {
 #pragma unroll
             for (int e = 0; e < V; ++e) zm[e] = T(0);
@@ -526,8 +579,8 @@ __device__ inline void pds_tile(const PdsB<T>& p, const PdsPtrs& P, unsigned cha
   }
 }
 
-template <typename T, int R, int MODE>
-__global__ void __launch_bounds__(kThreads, 4) pds_plane_kernel(PdsB<T> p, PdsPtrs P) {
+template <typename T, int R, int MODE, typename PP = PdsPtrs>
+__global__ void __launch_bounds__(kThreads, 4) pds_plane_kernel(PdsB<T> p, PP P) {
   using L = Layout<T, R>;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const unsigned tile = xcd_tile(blockIdx.x, p.ntiles);
@@ -539,45 +592,45 @@ __global__ void __launch_bounds__(kThreads, 4) pds_plane_kernel(PdsB<T> p, PdsPt
   const bool interior = p.vec_ok && (int64_t)p.g.n1 * p.g.n2 <= 0x7fffffff && ty0 - 2 * R >= 0 &&
                         ty0 + TY + 2 * R <= p.g.n1 && tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.g.n2;
   if (interior)
-    pds_tile<T, R, false, MODE>(p, P, smem_raw, img, ty0, tx0);
+    pds_tile<T, R, false, MODE, PP>(p, P, smem_raw, img, ty0, tx0);
   else
-    pds_tile<T, R, true, MODE>(p, P, smem_raw, img, ty0, tx0);
+    pds_tile<T, R, true, MODE, PP>(p, P, smem_raw, img, ty0, tx0);
 }
 
 // ------------------------------------------------------------------ host side
-template <typename T, int R0, bool PD3O>
+template <typename T, int R0, bool PD3O, typename GH = NoGhost>
 int launch_a(const PdsA<T>& pa, int np, int64_t M, int nseg, const void* src, const void* z, void* xo, void* q,
-             hipStream_t st) {
+             hipStream_t st, GH gh = GH()) {
   const int64_t blocks = (M + (int64_t)kAThreads * np - 1) / ((int64_t)kAThreads * np);
   dim3 grid((unsigned)blocks, (unsigned)nseg, (unsigned)pa.g.stack);
   if (np == 2)
-    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 2, PD3O>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
-                       (const T*)z, (T*)xo, (T*)q);
+    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 2, PD3O, GH>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
+                       (const T*)z, (T*)xo, (T*)q, gh);
   else
-    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 1, PD3O>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
-                       (const T*)z, (T*)xo, (T*)q);
+    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 1, PD3O, GH>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
+                       (const T*)z, (T*)xo, (T*)q, gh);
   return last_launch_status();
 }
 
-template <typename T, bool PD3O>
+template <typename T, bool PD3O, typename GH = NoGhost>
 int dispatch_a(int R0, const PdsA<T>& pa, int np, int64_t M, int nseg, const void* src, const void* z, void* xo,
-               void* q, hipStream_t st) {
+               void* q, hipStream_t st, GH gh = GH()) {
   switch (R0) {
-    case 0: return launch_a<T, 0, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 1: return launch_a<T, 1, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 2: return launch_a<T, 2, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 3: return launch_a<T, 3, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 4: return launch_a<T, 4, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 5: return launch_a<T, 5, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 6: return launch_a<T, 6, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    case 7: return launch_a<T, 7, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
-    default: return launch_a<T, 8, PD3O>(pa, np, M, nseg, src, z, xo, q, st);
+    case 0: return launch_a<T, 0, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 1: return launch_a<T, 1, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 2: return launch_a<T, 2, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 3: return launch_a<T, 3, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 4: return launch_a<T, 4, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 5: return launch_a<T, 5, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 6: return launch_a<T, 6, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    case 7: return launch_a<T, 7, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    default: return launch_a<T, 8, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
   }
 }
 
-template <typename T, int R, int MODE>
-int launch_b(const PdsB<T>& pb, const PdsPtrs& P, hipStream_t st) {
-  auto kern = pds_plane_kernel<T, R, MODE>;
+template <typename T, int R, int MODE, typename PP = PdsPtrs>
+int launch_b(const PdsB<T>& pb, const PP& P, hipStream_t st) {
+  auto kern = pds_plane_kernel<T, R, MODE, PP>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -589,17 +642,17 @@ int launch_b(const PdsB<T>& pb, const PdsPtrs& P, hipStream_t st) {
   return last_launch_status();
 }
 
-template <typename T, int MODE>
-int dispatch_b(int R, const PdsB<T>& pb, const PdsPtrs& P, hipStream_t st) {
+template <typename T, int MODE, typename PP = PdsPtrs>
+int dispatch_b(int R, const PdsB<T>& pb, const PP& P, hipStream_t st) {
   switch (R) {
-    case 1: return launch_b<T, 1, MODE>(pb, P, st);
-    case 2: return launch_b<T, 2, MODE>(pb, P, st);
-    case 3: return launch_b<T, 3, MODE>(pb, P, st);
-    case 4: return launch_b<T, 4, MODE>(pb, P, st);
-    case 5: return launch_b<T, 5, MODE>(pb, P, st);
-    case 6: return launch_b<T, 6, MODE>(pb, P, st);
-    case 7: return launch_b<T, 7, MODE>(pb, P, st);
-    default: return launch_b<T, 8, MODE>(pb, P, st);
+    case 1: return launch_b<T, 1, MODE, PP>(pb, P, st);
+    case 2: return launch_b<T, 2, MODE, PP>(pb, P, st);
+    case 3: return launch_b<T, 3, MODE, PP>(pb, P, st);
+    case 4: return launch_b<T, 4, MODE, PP>(pb, P, st);
+    case 5: return launch_b<T, 5, MODE, PP>(pb, P, st);
+    case 6: return launch_b<T, 6, MODE, PP>(pb, P, st);
+    case 7: return launch_b<T, 7, MODE, PP>(pb, P, st);
+    default: return launch_b<T, 8, MODE, PP>(pb, P, st);
   }
 }
 
@@ -609,6 +662,13 @@ int run_a(const PdsA<double>& pa, bool pd3o, int R0, int np, int64_t M, int nseg
           void* xo, void* q, hipStream_t st);
 int run_b(const PdsB<float>& pb, int mode, int R, const PdsPtrs& P, hipStream_t st);
 int run_b(const PdsB<double>& pb, int mode, int R, const PdsPtrs& P, hipStream_t st);
+// slab forms (pds_slab_f32.hip / pds_slab_f64.hip): kernel A with ghost planes, kernel B MODE 1 with the z_0 ghost
+int run_a_slab(const PdsA<float>& pa, const GhostA<float>& gh, bool pd3o, int R0, int np, int64_t M, int nseg,
+               const void* src, const void* z, void* xo, void* q, hipStream_t st);
+int run_a_slab(const PdsA<double>& pa, const GhostA<double>& gh, bool pd3o, int R0, int np, int64_t M, int nseg,
+               const void* src, const void* z, void* xo, void* q, hipStream_t st);
+int run_b_slab(const PdsB<float>& pb, int R, const PdsPtrsSlab& P, hipStream_t st);
+int run_b_slab(const PdsB<double>& pb, int R, const PdsPtrsSlab& P, hipStream_t st);
 
 }  // namespace pds
 }  // namespace pxa

@@ -27,6 +27,10 @@ steps the hot path has, and nothing else:
   local adjoint back to the neighbours, which add it to their edge planes.  Both are exact: the
   global operator restricted to the slab is Crop o S_local o HaloPad.
 
+  PD3O / Condat-Vu on two ``SlabLinOp`` (a separable stencil and the Gradient) run the fused step on the compact
+  slab instead: :func:`ghost_exchange` fills preallocated ghost buffers with the neighbours' planes (no padded
+  copy of the slab), and the kernels read them in place (``pxa_pds_slab_primal`` / ``pxa_pds_slab_dual``).
+
 Message sizes are a few doubles (stop checks), ``4·N·B`` bytes (C4: 256 KiB per right-hand side at
 N = 65 536) or a few planes (halos: R planes of n1·n2 values per neighbour): latency-bound on xGMI,
 so RCCL's default (LL/one-shot) protocols are the right choice.
@@ -47,6 +51,8 @@ __all__ = [
     "RowShardedLinOp",
     "halo_pad",
     "halo_reduce",
+    "ghost_buffers",
+    "ghost_exchange",
     "SlabLinOp",
 ]
 
@@ -315,6 +321,57 @@ def halo_pad(x, lo, hi, group=None):
     return out
 
 
+def _check_ghost_depth(nl, lo, hi, w, n_global=None):
+    """A ghost never reaches past the neighbouring slab.  With `n_global` the test covers every rank's slab
+    (shard_range is deterministic), so all ranks raise together instead of one leaving the others in a receive."""
+    thinnest = nl if n_global is None else min(shard_range(n_global, r, w)[1] - shard_range(n_global, r, w)[0]
+                                                for r in range(w))
+    if w > 1 and min(nl, thinnest) < max(lo, hi):
+        raise ValueError(f"slab of {min(nl, thinnest)} planes is thinner than the ghost depth ({lo}, {hi})")
+
+
+def ghost_buffers(x, lo, hi, group=None):
+    """Preallocated (lo_buf, hi_buf) for :func:`ghost_exchange` of slabs shaped like x (S, nl, M): (S, lo, M) and
+    (S, hi, M) tensors, None where this rank's slab touches the edge of the volume or the depth is 0."""
+    rank, w = world(group)
+    S, _, M = x.shape
+    return (_empty(x, (S, lo, M)) if rank > 0 and lo else None,
+            _empty(x, (S, hi, M)) if rank < w - 1 and hi else None)
+
+
+def ghost_exchange(x, lo, hi, group=None, out=None, n_global=None):
+    """Ghost planes of this rank's compact slab x (S, nl, M): returns (lo_buf, hi_buf), the last `lo` planes of
+    rank - 1's slab as (S, lo, M) and the first `hi` planes of rank + 1's as (S, hi, M); a side at the edge of the
+    volume (or of depth 0) comes back as None.  Unlike :func:`halo_pad` no padded copy of the slab is built: the
+    received messages land in the ghost buffers as they are, and only the planes sent are copied (not even those for
+    S = 1, where they are contiguous views).  `out` = buffers from :func:`ghost_buffers`, refilled in place (a solver
+    allocates them once); `n_global` = planes of the whole volume, for the thin-slab test on every rank."""
+    rank, w = world(group)
+    S, nl, M = x.shape
+    _check_ghost_depth(nl, lo, hi, w, n_global)
+    lo_buf, hi_buf = out if out is not None else ghost_buffers(x, lo, hi, group)
+    if w == 1:
+        return None, None
+    x = x if x.is_contiguous() else x.contiguous()
+    cut = (lambda p0, p1: x[:, p0:p1]) if S == 1 else (lambda p0, p1: _planes(x, p0, p1))
+    sends, recvs = [], []
+    if rank > 0:
+        if hi:
+            sends.append((cut(0, hi), rank - 1))  # rank - 1's hi ghost: my first planes
+        if lo:
+            recvs.append((lo_buf, rank - 1))
+    if rank < w - 1:
+        if lo:
+            sends.append((cut(nl - lo, nl), rank + 1))  # rank + 1's lo ghost: my last planes
+        if hi:
+            recvs.append((hi_buf, rank + 1))
+    for buf, d in ((lo_buf, lo), (hi_buf, hi)):
+        if buf is not None and (tuple(buf.shape) != (S, d, M) or buf.dtype != x.dtype or not buf.is_contiguous()):
+            raise ValueError(f"ghost buffer {tuple(buf.shape)} does not match depth {d} of a slab {tuple(x.shape)}")
+    _p2p(sends, recvs, group)
+    return (lo_buf if rank > 0 and lo else None), (hi_buf if rank < w - 1 and hi else None)
+
+
 def halo_reduce(xp, lo, hi, group=None):
     """Adjoint of halo_pad: xp (S, lo + nl + hi, M) -> (S, nl, M), the halo planes sent back to the
     neighbours that own them and added to their edge planes (dropped beyond the volume).  Each
@@ -365,6 +422,7 @@ class SlabLinOp(pxa.LinOp):
         self._halo = (int(halo[0]), int(halo[1]))
         self._group = group
         self._rows = (a, b)
+        self._global_shape = global_shape
         pshape = (self._halo[0] + self._nl + self._halo[1], *global_shape[1:])
         self._local = make_local(pshape)
         pdim = int(np.prod(pshape))
@@ -401,3 +459,20 @@ class SlabLinOp(pxa.LinOp):
         _dev_copy_rows(a, yp, S * K, nl * M, nl * M, P * M, 0, lo * M)
         xp = self._local.adjoint(yp.reshape(S, -1)).reshape(S, P, M)
         return halo_reduce(xp, lo, hi, self._group).reshape(*sh, nl * M)
+
+    def adjoint_gathered(self, arr):
+        """The adjoint in gather form, for a local operator that is ONE zero-boundary stencil (K = 1): its adjoint is
+        the stencil with the reach mirrored, so the slab's part of the global adjoint is Crop o S_local^T o
+        HaloPad with the halo (hi, lo).  Every output plane is then summed in the order of the unsharded adjoint
+        (same bits), where :meth:`adjoint` adds two partial sums on the planes next to a neighbour."""
+        if self._K != 1:
+            raise ValueError("adjoint_gathered needs a local operator with one output block (a stencil)")
+        (lo, hi), nl, M = self._halo, self._nl, self._M
+        sh, S = self._stack(arr)
+        P = lo + nl + hi
+        yp = halo_pad(arr.reshape(S, nl, M), hi, lo, self._group)
+        x = self._local.adjoint(yp.reshape(S, -1))
+        x = x if x.is_contiguous() else x.contiguous()
+        out = _empty(x, (S, nl * M))
+        _dev_copy_rows(x, out, S, nl * M, P * M, nl * M, hi * M, 0)
+        return out.reshape(*sh, nl * M)

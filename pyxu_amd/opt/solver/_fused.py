@@ -206,15 +206,34 @@ def match_pds_deblur(f, g, h, K, x0):
     if dt is None:
         return None
     H, shift = dt
-    sh = tuple(getattr(H, "_arg_shape", ()) or ())
-    if len(sh) not in (2, 3) or shift.ndim != 1:
-        return None
-    taps = _all_axis_taps(H, sh)
-    if taps is None:
-        return None
     G = _core(K)
-    if not isinstance(G, _DiffStack) or G._fused is None or tuple(G.arg_shape) != sh:
+    slab = _slab_pair(H, G)
+    if slab is False:
         return None
+    if slab is not None:
+        # halo-exchanged slabs of a volume (pyxu_amd.distributed.SlabLinOp): the taps of the local operators on the
+        # padded slab, the geometry of this rank's compact slab (the whole volume in a world of one process)
+        Hs, H, G = H, _core(H._local), _core(G._local)
+        psh = tuple(getattr(H, "_arg_shape", ()) or ())
+        if len(psh) != 3 or shift.ndim != 1 or not isinstance(G, _DiffStack) or tuple(G.arg_shape[1:]) != psh[1:]:
+            return None  # (each local operator lives on the slab padded with its own halo)
+        taps = _all_axis_taps(H, psh)
+        if taps is None or G._fused is None or tuple(G._directions) != (0, 1, 2):
+            return None
+        R0 = max(abs(v) for v in taps[0][0])
+        if min(Hs._halo) < R0:
+            return None  # the halo does not cover the stencil: S^T y and the generic operator would be wrong anyway
+        sh = (slab["nl"], *psh[1:])
+        H = Hs
+    else:
+        sh = tuple(getattr(H, "_arg_shape", ()) or ())
+        if len(sh) not in (2, 3) or shift.ndim != 1:
+            return None
+        taps = _all_axis_taps(H, sh)
+        if taps is None:
+            return None
+        if not isinstance(G, _DiffStack) or G._fused is None or tuple(G.arg_shape) != sh:
+            return None
     dirs = tuple(G._directions)
     if len(sh) == 2:
         if dirs != (0, 1):
@@ -252,5 +271,26 @@ def match_pds_deblur(f, g, h, K, x0):
     if x0.shape[-1] != N:
         return None
     rows = int(np.prod(x0.shape[:-1])) if x0.ndim > 1 else 1
-    return dict(shift=shift, H=H, taps=taps, n0=n0, n1=n1, n2=n2, D=D, c0=c0, c1=c1, lam=float(lam), h_kind=h_kind,
-                prox=gp[0], prox_scale=gp[1], rows=rows)
+    out = dict(shift=shift, H=H, taps=taps, n0=n0, n1=n1, n2=n2, D=D, c0=c0, c1=c1, lam=float(lam), h_kind=h_kind,
+               prox=gp[0], prox_scale=gp[1], rows=rows)
+    if slab is not None and slab["world"] > 1:
+        out["slab"] = slab  # (a world of one process is the plain unsharded problem on the whole volume)
+    return out
+
+
+def _slab_pair(H, G):
+    """f's operator and K as SlabLinOp of one volume and group: the slab geometry dict; None when neither is a
+    SlabLinOp (the unsharded case); False for everything that cannot be proven (generic path)."""
+    from pyxu_amd.distributed import SlabLinOp, world
+
+    hs, gs = isinstance(H, SlabLinOp), isinstance(G, SlabLinOp)
+    if not hs and not gs:
+        return None
+    if not (hs and gs):
+        return False
+    if H._global_shape != G._global_shape or H._group is not G._group or len(H._global_shape) != 3:
+        return False
+    if H._K != 1 or G._K != 3 or G._halo[1] < 1:  # (the forward difference reads one plane ahead)
+        return False
+    rank, w = world(H._group)
+    return dict(rank=rank, world=w, nl=H._nl, n_global=H._global_shape[0], group=H._group)

@@ -95,9 +95,14 @@ class _PrimalDualSplitting(pxa.Solver):
         p = match_pds_deblur(self._f, self._g, self._h, self._K, x0)
         if p is None:
             return None
+        if "slab" in p:
+            self._slab_depths(p)  # (raises on every rank for a slab thinner than its ghosts, before any exchange)
         mst = self._mstate
         y = _dev.axpby(-1.0, pxrt.coerce(p["shift"]))  # data y = -shift
-        p["hty"] = _dev.copy(p["H"].adjoint(y))  # S^T y: iteration-invariant (G x - S^T y = grad f(x))
+        # S^T y: iteration-invariant (G x - S^T y = grad f(x)); on a slab in gather form, which sums every plane in
+        # the unsharded order (SlabLinOp.adjoint_gathered)
+        adj = getattr(p["H"], "adjoint_gathered", p["H"].adjoint)
+        p["hty"] = _dev.copy(adj(y))
         stack = p["rows"]
         p["pre"] = _dev.pds_args(stack, 1, p["n0"], p["n1"], p["n2"], p["D"], p["taps"], p["c0"], p["c1"], mst["tau"],
                                  mst["sigma"], mst["rho"], p["lam"], p["prox"], mst["tau"] * p["prox_scale"], p["h_kind"])
@@ -105,9 +110,74 @@ class _PrimalDualSplitting(pxa.Solver):
         p["w"] = _dev.empty_like(x)
         p["q"] = None if p["taps"][0] == ([0], [1.0]) else _dev.empty_like(x)
         p["nseg"] = 0  # axis-0 march segments (0: one per column; tuning knob of pxa_pds_step)
-        p["la"] = bool(self._LOOKAHEAD)
+        p["la"] = bool(self._LOOKAHEAD) and "slab" not in p  # (no slab form of the look-ahead step)
         p["kt"] = _dev.empty_like(x) if p["la"] and self._FUSED_ALGO == 1 else None
+        if "slab" in p:
+            self._slab_plan(p)
         return p
+
+    def _slab_plan(self, p):
+        """Ghost depths and preallocated ghost buffers of the slab step (pxa_pds_slab_primal / _dual), and the
+        agreement of the step sizes over the ranks."""
+        import torch
+
+        import pyxu_amd.distributed as pxd
+
+        mst, sl = self._mstate, p["slab"]
+        rows, nl, M, D = p["rows"], p["n0"], p["n1"] * p["n2"], p["D"]
+        pd3o = self._FUSED_ALGO == 0
+        # every rank must iterate with the same step sizes: they come from beta and ||K||, which the slab operators
+        # take from the taps (not from the padded shape); one all-reduce proves it instead of assuming it
+        t = [float(mst[k]) for k in ("tau", "sigma", "rho")]
+        v = torch.tensor(t + [-a for a in t], dtype=torch.float64, device=mst["x"].device)
+        v = pxd.allreduce(v, "max", sl["group"]).tolist()
+        if any(a != -b for a, b in zip(v[:3], v[3:])):
+            raise ValueError(f"slab solver: tau / sigma / rho differ between the ranks (max {v[:3]}, "
+                             f"min {[-b for b in v[3:]]}); pass them explicitly")
+        x = mst["x"]
+        g = sl["group"]
+        sl["src_bufs"] = pxd.ghost_buffers(x.reshape(rows, nl, M), *sl["src"], group=g)
+        if pd3o:
+            sl["z_bufs"] = pxd.ghost_buffers(mst["z"].reshape(rows * D, nl, M), *sl["z"], group=g)
+        else:
+            sl["z_bufs"] = pxd.ghost_buffers(x.reshape(rows, nl, M)[:, :1], *sl["z"], group=g)
+        sl["w_bufs"] = pxd.ghost_buffers(x.reshape(rows, nl, M), *sl["w"], group=g)
+        sl["geom"] = (rows, nl, p["n1"], p["n2"], D)
+
+    def _slab_depths(self, p):
+        """(lo, hi) ghost depths of u / x, of z and of w: what the kernels read beyond the slab (include/pyxu_amd.h)."""
+        import pyxu_amd.distributed as pxd
+
+        sl = p["slab"]
+        R2 = 2 * max(abs(v) for v in p["taps"][0][0])
+        sl["src"] = (R2, R2)
+        sl["z"] = (R2 + 1, R2) if self._FUSED_ALGO == 0 else (1, 0)
+        sl["w"] = (0, 1)
+        pxd._check_ghost_depth(p["n0"], max(sl["src"][0], sl["z"][0]), max(R2, 1), sl["world"], sl["n_global"])
+
+    def _slab_step(self, x, u, z, x_out, u_out, z_out):
+        """One fused iteration on this rank's slab: exchange the ghosts of u / x and z, primal part (kernels A and
+        B), exchange w's first plane, dual part (kernel C)."""
+        import pyxu_amd.distributed as pxd
+
+        p, mst = self._plan, self._mstate
+        sl = p["slab"]
+        rows, nl, n1, n2, D = sl["geom"]
+        M, g, algo = n1 * n2, sl["group"], self._FUSED_ALGO
+        src = u if algo == 0 else x
+        src_lo = src_hi = None
+        if sl["src"][0]:
+            src_lo, src_hi = pxd.ghost_exchange(src.reshape(rows, nl, M), *sl["src"], group=g, out=sl["src_bufs"])
+        if algo == 0:
+            z_lo, z_hi = pxd.ghost_exchange(z.reshape(rows * D, nl, M), *sl["z"], group=g, out=sl["z_bufs"])
+        else:  # direction 0 of z on one plane: only that plane is handed to the exchange
+            z0 = z.reshape(rows, D, nl, M)[:, 0, nl - 1:]
+            z_lo, z_hi = pxd.ghost_exchange(z0 if rows == 1 else z0.contiguous(), *sl["z"], group=g, out=sl["z_bufs"])
+        _dev.pds_slab_primal(algo, p["pre"], x, u, z, p["hty"], x_out, u_out, p["q"], p["w"], src_lo, src_hi, z_lo,
+                             z_hi, nseg=p["nseg"])
+        _, w_hi = pxd.ghost_exchange(p["w"].reshape(rows, nl, M), *sl["w"], group=g, out=sl["w_bufs"])
+        _dev.pds_slab_dual(p["w"], z, sl["geom"], p["c0"], p["c1"], mst["sigma"], p["lam"], mst["rho"], p["h_kind"],
+                           relax=algo, w_hi=w_hi, out=z_out)
 
     # Two launches per iteration (pxa_pds_step_la: kernel B + the dual update fused with the next
     # iteration's axis-0 march) instead of three (pxa_pds_step); False selects the three-launch step.
@@ -238,7 +308,10 @@ class CondatVu(_PrimalDualSplitting):
             if out is None or out is x:
                 out = _dev.empty_like(x)
             z_out = z if self._owned(z, extra=1) else _dev.empty_like(z)
-            _dev.pds_step(1, p["pre"], x, None, z, p["hty"], out, None, z_out, p["q"], p["w"], nseg=p["nseg"])
+            if "slab" in p:
+                self._slab_step(x, None, z, out, None, z_out)
+            else:
+                _dev.pds_step(1, p["pre"], x, None, z, p["hty"], out, None, z_out, p["q"], p["w"], nseg=p["nseg"])
             mst["x"], mst["z"] = out, z_out
             self._spare = x if (sys.getrefcount(x) == 2 and _dev.storage_exclusive(x)) else None
             return
@@ -351,7 +424,10 @@ class PD3O(_PrimalDualSplitting):
             x_out = x if self._owned(x, extra=1) else _dev.empty_like(x)
             u_out = u if self._owned(u, extra=1) else _dev.empty_like(u)
             z_out = z if self._owned(z, extra=1) else _dev.empty_like(z)
-            _dev.pds_step(0, p["pre"], None, u, z, p["hty"], x_out, u_out, z_out, p["q"], p["w"], nseg=p["nseg"])
+            if "slab" in p:
+                self._slab_step(None, u, z, x_out, u_out, z_out)
+            else:
+                _dev.pds_step(0, p["pre"], None, u, z, p["hty"], x_out, u_out, z_out, p["q"], p["w"], nseg=p["nseg"])
             mst["x"], mst["u"], mst["z"] = x_out, u_out, z_out
             return
         tau, rho = mst["tau"], mst["rho"]
