@@ -58,11 +58,9 @@ extern "C" {
 #define PXA_MODE_SYMMETRIC 3
 #define PXA_MODE_EDGE 4
 
-/* Kernel-selection knobs (pxa_tuning). */
-#define PXA_TUNE_PGD_KERNEL 0 /* fused PGD step (pxa_pgd_tv2d_step / _plan_step): 0 / 1 the tile kernel (default); v >= 2 the
-                                * strip kernel with strips of v tiles (a workgroup walks a column strip, keeping the shared
-                                * window rows in LDS and prefetching each next tile's new rows; 16-B aligned rows only, else
-                                * the tile kernel).  Same bits; measured slower (A/B and tests only). */
+/* Kernel-selection knobs (pxa_tuning).  Keys 0, 6 and 12 are retired (they selected the strip kernel, the
+ * staggered-start probe and the pipelined kernel of the fused PGD step, all removed after losing their A/B
+ * measurements): pxa_tuning returns PXA_ERR_ARG for them, and the numbers are not reused. */
 #define PXA_TUNE_NORMAL_KERNEL 1 /* A/B of pxa_dense_normal: 0 row-split kernel (each row in four column parts,
                                     one workgroup each, part-dots exchanged), 1 one workgroup per row (results
                                     equal up to summation order), 2 the row-split kernel computing every part-dot
@@ -76,8 +74,6 @@ extern "C" {
                               library ignores it): bit 5 s_memtime phase trace (pxa_pgd_tile_trace); timing probes
                               with WRONG results: bit 6 skips passes A / B, bit 7 the window loads, bit 8 loads x only,
                               bit 9 the H^T y loads, bit 10 the x_new stores (scripts/pgd_modes_probe.py diag) */
-#define PXA_TUNE_PGD_STAGGER 6 /* fused PGD tile kernel A/B probe, PROBE BUILD ONLY: v = (sel << 8) | n delays the
-                                  workgroups picked by `sel` in the first dispatch round by n x 1024 cycles */
 #define PXA_TUNE_PDS_EVENTS 5 /* measurement hook: > 0 makes pxa_pds_step record HIP events around each
                                  of its kernels (pxa_pds_kernel_ms) */
 #define PXA_TUNE_PDS_MARCH 7 /* A/B of pxa_pds_step_la's kernel D: bit 0 lets a thread own two positions
@@ -106,11 +102,7 @@ extern "C" {
                                 * neighbours are its own rows), 8 the plane-block kernel (3-D fp32 16-B vectors: an 8 x 128
                                 * block of each plane staged in LDS with its halo row / column; 9: the same with z loaded one plane ahead).  Same
                                 * bits. */
-#define PXA_TUNE_PGD_PIPE 12 /* A/B of the fused PGD step: 1 the pipelined kernel (two resident workgroups per CU, each
-                               * walking its XCD's tiles, the next tile's x / x_prev window fetched by LDS-DMA into a
-                               * staging area during the current tile; fp32, 16-B aligned rows, R <= 7).  Same bits;
-                               * measured slower (profiles/r06n_pgd_pipe_ab.txt). */
-#define PXA_TUNE_COUNT 13
+#define PXA_TUNE_COUNT 13 /* (one past the highest key ever assigned, retired ones included) */
 
 /* Row reductions (pxa_row_reduce). */
 #define PXA_RED_SUMSQ 0  /* sum x^2            : SquaredL2Norm.apply, norm(ord=2)^2   (norm.py:91-94) */
@@ -132,7 +124,7 @@ const char* pxa_error_string(int code);
 int pxa_abi_version(void);
 
 /* Process-wide kernel-selection knob `key` (PXA_TUNE_*): sets it to `value` when value >= 0 and
- * returns the previous value (PXA_ERR_ARG for an unknown key).  Defaults (0) pick the fastest
+ * returns the previous value (PXA_ERR_ARG for an unknown or retired key).  Defaults (0) pick the fastest
  * kernel; the other values exist for A/B measurements and the parity tests between variants. */
 int pxa_tuning(int key, int value);
 
@@ -533,8 +525,7 @@ int pxa_dir_contract(int dtype, int64_t S, int64_t G, int64_t J, int64_t K, int6
  * iterate of the previous check (opt/stop.py:353-382) — pxa_pgd_tv2d_partials_count() gives the
  * number of slots (tiles x 4; the slots of one image are contiguous).  prox codes: 0 none, 1 positive
  * orthant, 2 l1 with weight prox_w.  pxa_pgd_tv2d_last_kernel() is the kernel the calling thread launched
- * last: 1 the tile kernel, 2 the strip kernel (PXA_TUNE_PGD_KERNEL), 3 the pipelined kernel (PXA_TUNE_PGD_PIPE), 0 none
- * yet.
+ * last: 1 the tile kernel (the only one; 2 and 3 were the removed strip and pipelined kernels), 0 none yet.
  * ------------------------------------------------------------------------------------------- */
 int pxa_pgd_tv2d_partials_count(int64_t stack, int64_t n0, int64_t n1);
 /* Prepared form of pxa_pgd_tv2d_step for a solver's iterations (replaces the same call per PGD.m_step,

@@ -25,8 +25,11 @@ const char* pxa_error_string(int code) {
 // Process-wide kernel-selection knobs (A/B measurements and parity tests of kernel variants).
 static int g_tuning[PXA_TUNE_COUNT] = {0};
 
+// keys whose kernel variants were removed (pyxu_amd.h): an error, so that a stale A/B script does not time the default
+static bool retired_key(int key) { return key == 0 || key == 6 || key == 12; }
+
 int pxa_tuning(int key, int value) {
-  if (key < 0 || key >= PXA_TUNE_COUNT) return PXA_ERR_ARG;
+  if (key < 0 || key >= PXA_TUNE_COUNT || retired_key(key)) return PXA_ERR_ARG;
   const int prev = g_tuning[key];
   if (value >= 0) g_tuning[key] = value;
   return prev;

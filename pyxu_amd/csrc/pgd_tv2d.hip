@@ -50,9 +50,9 @@
 #define PXA_PGD_PRIO_FIN 0  // (A/B builds: the finishing row-major epilogue)
 #endif
 
-// Measurement probes (s_memtime phase trace, skip probes, staggered starts: PXA_TUNE_PGD_DIAG /
-// PXA_TUNE_PGD_STAGGER) exist only in the probe build (`make -C pyxu_amd/csrc probe`, scripts/ that time
-// kernel phases); the production library compiles them out, so its kernel carries no probe branch.
+// Measurement probes (s_memtime phase trace, skip probes: PXA_TUNE_PGD_DIAG) exist only in the probe build
+// (`make -C pyxu_amd/csrc probe`, scripts/ that time kernel phases); the production library compiles them out, so
+// its kernel carries no probe branch.
 #ifndef PXA_PROBES
 #define PXA_PROBES 0
 #endif
@@ -77,10 +77,8 @@ struct PgdParams {
   int prox;  // 0 none, 1 positive orthant, 2 l1 (uniform branch)
   bool tv;   // lam != 0 (uniform branch)
   bool vec_ok;
-  int diag;     // PXA_TUNE_PGD_DIAG (bit 5: s_memtime phase trace of a few workgroups)
-  int stagger;  // PXA_TUNE_PGD_STAGGER (A/B probe: delayed start of some first-round workgroups)
-  unsigned round1;  // workgroups resident at once (4 per CU)
-  const T* xref;    // RelError partials relative to this iterate (nullptr: relative to x)
+  int diag;       // PXA_TUNE_PGD_DIAG (bit 5: s_memtime phase trace of a few workgroups)
+  const T* xref;  // RelError partials relative to this iterate (nullptr: relative to x)
   // last-workgroup fold of the RelError partials (pxa_pgd_tv2d_plan_step with rel_values): the workgroup
   // that finishes last folds them as pxa_tile_partials_fold does (same bits) into fold_vals (host-mapped,
   // (2, fold_rows)) and sets fold_flags[q] = fold_seq; `counter` (device, 0 between launches) counts the
@@ -90,10 +88,6 @@ struct PgdParams {
   unsigned* counter;
   unsigned fold_seq;
   int64_t fold_rows, fold_per_row;
-  // strip kernel (pgd_strip_kernel): tiles per strip, strip groups per tile column of an image, strips in all
-  unsigned slen, sgroups, nstrips;
-  // pipelined kernel (pgd_pipe_kernel): resident tile workgroups (0: not that kernel)
-  unsigned pipe_wgs;
   // window partials (pxa_pgd_tv2d_plan_step_wfold): the per-(tile, wave) partials are (sum (x - x_prev)^2, sum x_prev^2)
   // over the tile, from the window loads -- the RelError statistics of the PREVIOUS step's check -- instead of the
   // epilogue's (x_new - x_ref) statistics: no extra load of x
@@ -170,7 +164,6 @@ struct Window {
   static constexpr int HS = (K0 - KI) * NW;  // halo wave-slots that K0 items leave
   static constexpr bool SIDE_ROWS = cdiv(L::AR, SRB) + NVS <= HS;
   static constexpr int NSS = SIDE_ROWS ? cdiv(L::AR, SRB) : SL;  // side slots
-  static constexpr int NSLOT = KI * NW + NSS + NVS;              // wave-slots in use
   static_assert(NI % kThreads == 0, "every thread loads KI of the tile's own vectors");
   static_assert(64 % TV == 0 && RPW % 2 == 0 && (4 * R) % RPW == 0, "vert slots: whole rows, top / bottom pairs");
   static_assert(SL <= 64 && L::AR <= 64, "side slots: a row block or a column per wave");
@@ -310,15 +303,6 @@ __device__ inline void win_store(const PgdParams<T>& p, T* A, const Window<T, R>
   }
 }
 
-template <typename T, int R, bool EDGE>
-__device__ inline void load_window(const PgdParams<T>& p, T* A, int ty0, int tx0, const T* __restrict__ xs,
-                                   const T* __restrict__ xps) {
-  Window<T, R> w;
-  const int tid = threadIdx.x;
-  win_issue<T, R, EDGE>(p, ty0, tx0, xs, xps, w, tid);
-  win_store<T, R>(p, A, w, tid);
-}
-
 // ---- pass A: PT[col][row] = (G0 yk)[row][col] for the TY tile rows and all A columns
 template <typename T, int R, bool EDGE, int D = 0>
 __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T* KT, int ty0, int tid = threadIdx.x) {
@@ -367,7 +351,7 @@ constexpr int kTvxFloats = 9 * 16 + 9 * 32;  // per wavefront: q0 [row group + 1
 
 template <typename T, int R, bool EDGE>
 __device__ inline void tv_exchange(const PgdParams<T>& p, T* A, int ty0, int tx0, int tid, int a, int cb,
-                                   T (&yc)[kVecN<T>][2], T (&tv)[kVecN<T>][2], T* xarea23) {
+                                   T (&yc)[kVecN<T>][2], T (&tv)[kVecN<T>][2]) {
   using L = Layout<T, R>;
   constexpr int V = L::V;
   constexpr int CA = L::CA;
@@ -405,9 +389,8 @@ __device__ inline void tv_exchange(const PgdParams<T>& p, T* A, int ty0, int tx0
 #pragma unroll
     for (int w = 0; w < 2; ++w)
       qat(y[u][w], y[u + 1][w], y[u][w + 1], ty0 + V * a + u, tx0 + c0 + w, q0[u][w], q1[u][w]);
-  // exchange area of this wavefront: waves 0, 1 in A's top dead rows, 2, 3 in the bottom ones -- or, in the strip
-  // kernel (whose bottom window rows are the next tile's top rows), in `xarea23` beside the tile's LDS carve
-  T* E = (wv < 2 ? A : xarea23 != nullptr ? xarea23 : A + (TY + 2 * R + 1) * L::AP) + (wv & 1) * kTvxFloats;
+  // exchange area of this wavefront: waves 0, 1 in A's top dead rows, 2, 3 in the bottom ones
+  T* E = (wv < 2 ? A : A + (TY + 2 * R + 1) * L::AP) + (wv & 1) * kTvxFloats;
   T* E0 = E;            // [a + 1][col within the wavefront's 16]
   T* E1 = E + 9 * 16;   // [col item + 1][row]
   // halo of the wavefront: lanes 0..15 the q0 of tile row -1 (its 16 columns), lanes 16..47 the q1 of the column
@@ -455,7 +438,7 @@ __device__ inline void tv_exchange(const PgdParams<T>& p, T* A, int ty0, int tx0
 // coalesced epilogue (epilogue_staged).
 template <typename T, int R, bool EDGE, typename Emit, int D = 0>
 __device__ inline void pass_b(const PgdParams<T>& p, const T* A, const T* PT, const T* KT, const T* GH, int ty0, int tx0,
-                              Emit&& emit, int tid = threadIdx.x, T* xarea23 = nullptr) {
+                              Emit&& emit, int tid = threadIdx.x) {
   using L = Layout<T, R>;
   constexpr int V = L::V;
   constexpr int CA = L::CA;
@@ -508,7 +491,7 @@ __device__ inline void pass_b(const PgdParams<T>& p, const T* A, const T* PT, co
       constexpr bool kX = PXA_PGD_TVX && sizeof(T) == 4 && L::NA == 8 && CW == 2 && KB == 1 &&
                           (2 * R - 1) * L::AP >= kTvxFloats * 2;
       if constexpr (kX) {
-        tv_exchange<T, R, EDGE>(p, const_cast<T*>(A), ty0, tx0, tid, a, cb, yc, tv, xarea23);
+        tv_exchange<T, R, EDGE>(p, const_cast<T*>(A), ty0, tx0, tid, a, cb, yc, tv);
       } else {
         T yr[CW + 2], yn[CW + 2];
         yrow(0, yr);
@@ -664,45 +647,17 @@ __device__ inline void wave_partials(double part_d, double part_x, double* parti
   }
 }
 
-// Prefetch point of the strip kernel's next-window rows inside a tile (PXA_PGD_STRIP_ISSUE): 0 right after pass A
-// (the loads overlap pass B and the epilogue, and occupy registers through pass B), 1 after the epilogue's own
-// loads (they overlap the O staging and the finishing stores only).
-#ifndef PXA_PGD_STRIP_ISSUE
-#define PXA_PGD_STRIP_ISSUE 1
-#endif
-// Rows in flight per G sweep (tile2d.hpp sweep's D): 0 = compiler-scheduled (tile kernel default); the strip kernel
-// limits it so that its prefetched rows fit beside the passes in 128 VGPRs
+// Rows in flight per G sweep (tile2d.hpp sweep's D): 0 = compiler-scheduled (default); A/B builds limit it
 #ifndef PXA_PGD_SWEEP_DEPTH
 #define PXA_PGD_SWEEP_DEPTH 0
 #endif
-#ifndef PXA_PGD_STRIP_DEPTH
-#define PXA_PGD_STRIP_DEPTH 6
-#endif
-
-struct NoHook {
-  __device__ void operator()() const {}
-};
-
-// Workgroup barrier of a tile body.  RB: the raw form (LDS operations complete, then s_barrier) for the pipelined
-// kernel, whose next window is in flight by LDS-DMA during the body -- __syncthreads()'s fence would wait for it
-// (an LDS-DMA is a pending LDS write on the VM counter) at every barrier.  The body's own global loads land in
-// registers, which the compiler waits for at their use, so the raw form orders everything the body shares.
-template <bool RB>
-__device__ inline void body_sync() {
-  if constexpr (RB) {
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  } else {
-    __syncthreads();
-  }
-}
 
 // The phases of one output tile once its window is in A (behind a barrier): pass A, [ghost columns], pass B
-// (parked in registers), the H^T y / x loads, O staging, row-major epilogue, [RelError partials].  `mid` runs at the
-// strip kernel's prefetch point; `xarea23`: see tv_exchange (nullptr in the tile kernel).
-template <typename T, int R, bool EDGE, int D, bool RB, typename Mid>
+// (parked in registers), the H^T y / x loads, O staging, row-major epilogue, [RelError partials].
+template <typename T, int R, bool EDGE, int D>
 __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
                                      const T* __restrict__ bs, T* __restrict__ xns, double* __restrict__ partials,
-                                     const T* __restrict__ xrs, T* xarea23, Mid&& mid, const int tid) {
+                                     const T* __restrict__ xrs, const int tid) {
   using L = Layout<T, R>;
   using S = Stage<T, R>;
   constexpr int CW = L::CW;
@@ -716,7 +671,7 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
   const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
   double part_d = 0.0, part_x = 0.0;
   const bool want_part = partials != nullptr;
-  const bool tracing = kProbes && (p.diag & 32) != 0 && xarea23 == nullptr;
+  const bool tracing = kProbes && (p.diag & 32) != 0;
   unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kGhBytes<T, R>);
   auto tmark = [&](int pt) {
     if (tracing && (tid & 63) == 0) ts[(tid >> 6) * 8 + pt] = clock64();
@@ -725,11 +680,10 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
   const bool skip_passes = kProbes && (p.diag & 64) != 0;  // timing probe only (WRONG results)
   if (!skip_passes) pass_a<T, R, EDGE, D>(p, A, PT, KT, ty0, tid);
   tmark(3);
-  body_sync<RB>();
-  if (PXA_PGD_STRIP_ISSUE == 0) mid();
+  __syncthreads();
   if (edge_cols) {
     ghost_cols_coop<T, R>(p.k1, PT, GH, tx0, n1, tid);
-    body_sync<RB>();
+    __syncthreads();
   }
   tmark(4);
   T st[KB][V][CW];
@@ -746,7 +700,7 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
 #pragma unroll
       for (int w = 0; w < CW; ++w) st[k][u][w] = g[w];
     };
-    pass_b<T, R, EDGE, decltype(park)&, D>(p, A, PT, KT, GH, ty0, tx0, park, tid, xarea23);
+    pass_b<T, R, EDGE, decltype(park)&, D>(p, A, PT, KT, GH, ty0, tx0, park, tid);
   }
   StagedB<T, R> hb;
   if (kProbes && (p.diag & 512)) {  // timing probe only (WRONG results): no H^T y loads
@@ -764,7 +718,7 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
 #endif
   }
   tmark(5);
-  body_sync<RB>();  // every G1 sweep is done with PT: O may overwrite it
+  __syncthreads();  // every G1 sweep is done with PT: O may overwrite it
   T* O = PT;
 #pragma unroll
   for (int k = 0; k < KB; ++k) {
@@ -787,8 +741,7 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
   }
   // x (RelError partials only) is loaded once pass B's parked results are out of the registers
   if (want_part) load_staged<T, R, EDGE>(p, ty0, tx0, xrs, hb.x, tid);
-  if (PXA_PGD_STRIP_ISSUE != 0) mid();
-  body_sync<RB>();
+  __syncthreads();
   tmark(6);
 #if PXA_PGD_PRIO_FIN
   __builtin_amdgcn_s_setprio(PXA_PGD_PRIO_FIN);  // A/B builds: the finishing stores ahead of other passes
@@ -882,14 +835,14 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
 #endif
   tmark(1);
   __syncthreads();
-  // fp64: the thread index laundered between the window and the body (as the strip kernel does per tile), so that the
-  // body derives its lane values afresh instead of sharing them with the window phase and keeping them live across it:
-  // no scratch up to R = 6 and 84-117 VGPRs where sharing them spilled (profiles/pgd_window_isa.txt).  fp32 shares them:
-  // laundering there costs ~30 static VALU and changes nothing at R <= 6.
+  // fp64: the thread index laundered between the window and the body, so that the body derives its lane values afresh
+  // instead of sharing them with the window phase and keeping them live across it: no scratch up to R = 6 and 84-117
+  // VGPRs where sharing them spilled (profiles/pgd_window_isa.txt).  fp32 shares them: laundering there costs ~30
+  // static VALU and changes nothing at R <= 6.
   int btid = tid;
   if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(btid));
-  pgd_tile_body<T, R, EDGE, PXA_PGD_SWEEP_DEPTH, false>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
-                                                 nullptr, NoHook{}, btid);
+  pgd_tile_body<T, R, EDGE, PXA_PGD_SWEEP_DEPTH>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
+                                                 btid);
 }
 
 // (Opt-in: PXA_RELERR_SINK=1; gfx950-specific.)  The hand-off below uses no release / acquire: it is the first row
@@ -966,12 +919,6 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
   }
   const unsigned vb = blockIdx.x - pub;
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  if (kProbes && p.stagger && blockIdx.x < p.round1) {
-    const unsigned sel = (unsigned)p.stagger >> 8, b = blockIdx.x >> 3;  // b: index within the XCD
-    const bool late = sel == 1 ? (b & 1u) : sel == 2 ? ((b >> 1) & 1u) : sel == 3 ? ((b >> 2) & 1u) : ((b >> 5) & 1u);
-    if (late)
-      for (int i = 0; i < (p.stagger & 255); ++i) __builtin_amdgcn_s_sleep(16);
-  }
   unsigned tile = xcd_tile(vb, p.ntiles);
   {  // the last XCD band walks backwards: an image's bottom-edge tiles (slower: boundary corrections)
      // are dispatched first instead of last, longest-first scheduling (2048^2: 29.2-29.3 -> 28.9-29.0 us)
@@ -1006,383 +953,9 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
 
 thread_local int g_last_pgd_kernel = 0;  // pxa_pgd_tv2d_last_kernel
 
-// ---- strip kernel: one workgroup walks a column strip of `slen` tiles downwards, keeping the window rows two
-// vertically adjacent tiles share.  Tile i + 1's window (rows ty0 + TY - 2R .. ty0 + 2 TY + 2R) overlaps tile i's in
-// 4R rows; only its TY new rows are loaded -- issued into registers while tile i computes (PXA_PGD_STRIP_ISSUE), so
-// their latency overlaps pass B / the epilogue instead of opening the next tile -- then, once tile i's epilogue is
-// done, the 4R shared rows move up in LDS (rows TY.. -> 0..) and the new rows are written below them as yk.  Per tile
-// the arithmetic is the tile kernel's (same functions, same order): x_new and the RelError partials are bit-identical
-// (tests/test_gpu_pgd_variants.py).  LDS: the tile carve + the TV-exchange area of waves 2, 3 (the tile kernel puts
-// it in the window's bottom dead rows, which here are the next tile's top rows): 39.8 KB, four workgroups per CU.
-// MEASURED SLOWER, kept opt-in for A/B (PXA_TUNE_PGD_KERNEL = strip length; round 6, profiles/r06b_pgd_strip_ab.txt):
-// 2048^2 29.8 us against 23.9-25.2 (strips of 2), 4096^2 93.7 against 71.6 (8), C5 0.640 against 0.631 ms (16).  The
-// prefetch can only be issued after the epilogue's own loads (held through pass B, the rows need ~24 VGPRs the
-// passes do not have: 66 spilled), so it hides little; the loop keeps ~170 SGPRs of parameters and strip state live
-// (spilled to VGPR lanes: a v_readlane before many tap uses in the sweeps); and the four workgroups of a CU walk their
-// strips in lockstep for the whole launch, where the tile kernel's second round starts de-phased.  R 7, 8 spill VGPRs.
-template <typename T, int R>
-struct NewRows {  // the next tile's TY new window rows of x and x_prev, per thread
-  using L = Layout<T, R>;
-  static constexpr int NR = TY * L::NGA;
-  static constexpr int K1 = cdiv(NR, kThreads);
-  T xv[K1][L::V], pv[K1][L::V];
-};
-
-// Branch-free: every lane loads a whole 16-B vector from an address clamped into the image and zeroes it when the
-// vector lies outside (the strip kernel runs only with vec_ok: rows 16-B aligned, n1 % V == 0, so a window vector is
-// wholly inside or wholly outside) -- no exec-masked loads, whose results the compiler waited for and spilled.
-template <typename T, int R>
-__device__ inline void rows_issue(const PgdParams<T>& p, int ty0n, int tx0, const T* __restrict__ xs,
-                                  const T* __restrict__ xps, NewRows<T, R>& w, const int lt) {
-  using L = Layout<T, R>;
-  constexpr int V = L::V;
-  const int n0 = p.n0, n1 = p.n1;
-#pragma unroll
-  for (int k = 0; k < NewRows<T, R>::K1; ++k) {
-    int it = lt + k * kThreads;
-    if (it >= NewRows<T, R>::NR) it = NewRows<T, R>::NR - 1;  // (surplus lanes of the last batch: dropped later)
-    const int r = it / L::NGA, g = it - r * L::NGA;
-    const int gr = ty0n + 2 * R + r, gc = tx0 - L::CA + V * g;  // window row 4R + r of the tile at ty0n
-    const bool in = gr >= 0 && gr < n0 && gc >= 0 && gc < n1;
-    const int cr = gr < 0 ? 0 : gr >= n0 ? n0 - 1 : gr, cc = gc < 0 ? 0 : gc >= n1 ? n1 - V : gc;
-    const int64_t off = (int64_t)cr * n1 + cc;
-    ld_vec<T, V>(xs + off, w.xv[k]);
-    ld_vec<T, V>(xps + off, w.pv[k]);
-#pragma unroll
-    for (int v = 0; v < V; ++v) {
-      w.xv[k][v] = in ? w.xv[k][v] : T(0);
-      w.pv[k][v] = in ? w.pv[k][v] : T(0);
-    }
-  }
-}
-
-// Next window, behind a barrier that follows every read of A by the current tile: the 4R rows shared with the next
-// tile move up (rows TY .. TY + 4R - 1 -> 0 .. 4R - 1: disjoint ranges, so each thread copies its vectors directly),
-// a barrier, then the new rows go in below them as yk (4R .. AR - 1, which overlaps the copy's source rows).
-template <typename T, int R>
-__device__ inline void window_advance(const PgdParams<T>& p, T* A, const NewRows<T, R>& w, const int lt) {
-  using L = Layout<T, R>;
-  constexpr int V = L::V;
-  using VT = typename Vec4<T>::type;
-  constexpr int NS = 4 * R * L::NGA;
-  VT* A4 = reinterpret_cast<VT*>(__builtin_assume_aligned(A, 16));
-#pragma unroll
-  for (int k = 0; k < cdiv(NS, kThreads); ++k) {
-    const int it = lt + k * kThreads;
-    if (it < NS) {
-      const int r = it / L::NGA, g = it - r * L::NGA;
-      A4[(r * L::AP) / V + g] = A4[((TY + r) * L::AP) / V + g];
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < NewRows<T, R>::K1; ++k) {
-    const int it = lt + k * kThreads;
-    if (it < NewRows<T, R>::NR) {
-      const int r = it / L::NGA, g = it - r * L::NGA;
-      T out[V];
-#pragma unroll
-      for (int v = 0; v < V; ++v) out[v] = fma(w.xv[k][v] - w.pv[k][v], p.a, w.xv[k][v]);  // as win_store
-      st_vec<T, V>(A + (4 * R + r) * L::AP + V * g, out);
-    }
-  }
-}
-
-template <typename T, int R>
-constexpr size_t kStripXOff = kGhOff<T, R> + kGhBytes<T, R>;  // the TV-exchange area of waves 2, 3
-constexpr size_t kStripXBytes = (size_t)2 * kTvxFloats * sizeof(float);
-
-template <typename T, int R>
-__global__ void __launch_bounds__(kThreads, 4) pgd_strip_kernel(PgdParams<T> p, const T* __restrict__ x,
-                                                             const T* __restrict__ xp, const T* __restrict__ b,
-                                                             T* __restrict__ xn, double* __restrict__ partials) {
-  using L = Layout<T, R>;
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  T* A = reinterpret_cast<T*>(smem_raw);
-  T* KT = A + L::AR * L::AP + L::AC * L::PTP;
-  T* X23 = reinterpret_cast<T*>(smem_raw + kStripXOff<T, R>);
-  const int tid = threadIdx.x;
-  if (tid < 2 * R + 1) {
-    KT[tid] = p.k0[tid];
-    KT[kKT + tid] = p.k1[tid];
-  }
-  unsigned strip = xcd_tile(blockIdx.x, p.nstrips);
-  {  // the last XCD band walks backwards (longest-first: the bottom-edge strips), as in the tile kernel
-    const unsigned nb = p.nstrips, q8 = nb >> 3, r8 = nb & 7u, g8 = blockIdx.x & 7u;
-    if (g8 == 7u) {
-      const unsigned lo = 7u * q8 + (r8 < 7u ? r8 : 7u), len = q8 + (7u < r8 ? 1u : 0u);
-      strip = lo + (len - 1u - (strip - lo));
-    }
-  }
-  // strip = (image, strip group, tile column), tile column fastest: an XCD's band spans whole strip rows, so the
-  // column halos of neighbouring strips are L2 hits
-  const unsigned tiles1 = (unsigned)p.tiles1, per_img = p.sgroups * tiles1;
-  const unsigned si = strip / per_img, rem = strip - si * per_img;
-  const unsigned sg = rem / tiles1, tc = rem - sg * tiles1;
-  const int tr0 = (int)(sg * p.slen);
-  const int tr1 = tr0 + (int)p.slen < p.tiles0 ? tr0 + (int)p.slen : p.tiles0;
-  const int tx0 = (int)tc * TX;
-  const int64_t img = (int64_t)p.n0 * p.n1;
-  const T* xs = x + (int64_t)si * img;
-  const T* xps = xp + (int64_t)si * img;
-  const T* bs = b + (int64_t)(si % (unsigned)p.y_images) * img;
-  T* xns = xn + (int64_t)si * img;
-  const T* xrs = (p.xref != nullptr ? p.xref : x) + (int64_t)si * img;
-  const unsigned tpi = (unsigned)p.tiles0 * tiles1;
-  const bool cols_in = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;
-  {
-    const int ty0 = tr0 * TY;
-#if PXA_PGD_PRIO
-    __builtin_amdgcn_s_setprio(PXA_PGD_PRIO);
-#endif
-    if (cols_in && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0) load_window<T, R, false>(p, A, ty0, tx0, xs, xps);
-    else load_window<T, R, true>(p, A, ty0, tx0, xs, xps);
-#if PXA_PGD_PRIO
-    __builtin_amdgcn_s_setprio(0);
-#endif
-  }
-  NewRows<T, R> nw;
-  for (int tr = tr0; tr < tr1; ++tr) {
-    // the thread index laundered per tile: its derived addresses are recomputed in every tile instead of being
-    // hoisted out of the loop and kept live across it (the loop-invariant form spilled ~70-200 VGPRs)
-    int ltid = tid;
-    asm volatile("" : "+v"(ltid));
-    const int ty0 = tr * TY;
-    const unsigned tile = si * tpi + (unsigned)tr * tiles1 + tc;
-    const bool more = tr + 1 < tr1;
-    __syncthreads();  // the window of this tile is in A
-    // (issued for the last tile of the strip too, clamped into the image, so that no branch guards the loads)
-    auto issue = [&]() { rows_issue<T, R>(p, ty0 + TY, tx0, xs, xps, nw, ltid); };
-    if (cols_in && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0)
-      pgd_tile_body<T, R, false, PXA_PGD_STRIP_DEPTH, false>(p, smem_raw, tile, ty0, tx0, bs, xns, partials, xrs, X23, issue, ltid);
-    else
-      pgd_tile_body<T, R, true, PXA_PGD_STRIP_DEPTH, false>(p, smem_raw, tile, ty0, tx0, bs, xns, partials, xrs, X23, issue, ltid);
-    if (more) {
-      __syncthreads();  // every read of this window is done
-      window_advance<T, R>(p, A, nw, ltid);
-    }
-  }
-  if (p.fold_vals != nullptr) tail_fold<T>(p, partials);
-}
-
-template <typename T, int R>
-int launch_pgd_strip(const PgdParams<T>& p, const void* x, const void* xp, const void* b, void* xn, double* partials,
-                     hipStream_t s) {
-  const size_t smem = kStripXOff<T, R> + kStripXBytes;
-  auto kern = pgd_strip_kernel<T, R>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.nstrips), dim3(kThreads), smem, s, p, (const T*)x, (const T*)xp, (const T*)b,
-                     (T*)xn, partials);
-  return last_launch_status();
-}
-
-// ---- pipelined kernel (PXA_TUNE_PGD_KERNEL = -1): a resident grid of two workgroups per CU, each walking the tiles of
-// its XCD's band (i = blockIdx.x, + grid, ...: the same XCD every time).  The raw x / x_prev window of the NEXT tile is
-// fetched by LDS-DMA (global_load_lds_dwordx4: no VGPR destination, so nothing is held through the passes) into a
-// staging area beside the tile carve while the current tile runs passes A / B and its epilogue; then one pass turns
-// the staged window into yk in A (win_store's arithmetic: the same bits as the tile kernel's phase 0).  The body
-// uses raw barriers (body_sync<true>) so that the fetch stays in flight through them.  LDS: carve 36.4 KB + staging
-// 40 KB = 75.5 KB per workgroup (fp32, R = 6), two per CU; edge tiles are fetched with clamped addresses and their
-// outside vectors zeroed (vec_ok: a 16-B vector lies wholly inside or outside the image).
-template <typename T, int R>
-constexpr int kPipeChunks = Window<T, R>::NSLOT;  // one LDS-DMA wave-instruction = one wave-slot of the window order
-template <typename T, int R>
-constexpr size_t kPipeArr = (size_t)kPipeChunks<T, R> * 64 * 16;  // bytes of one staged window array
-template <typename T, int R>
-constexpr size_t kPipeRawOff = (kGhOff<T, R> + kGhBytes<T, R> + 15) / 16 * 16;
-template <typename T, int R>
-constexpr size_t kPipeBytes = kPipeRawOff<T, R> + 2 * kPipeArr<T, R>;
-
-template <typename T, int R>
-__device__ inline void pipe_issue(const PgdParams<T>& p, unsigned char* raw, int ty0, int tx0, const T* __restrict__ xs,
-                                  const T* __restrict__ xps, const int tid) {
-  using L = Layout<T, R>;
-  constexpr int V = L::V;
-  constexpr int NW = kThreads / 64;
-  static_assert(V * sizeof(T) == 16, "one 16-B vector per lane");
-  int wv, ln;
-  wave_lane(tid, wv, ln);
-  const int n0 = p.n0, n1 = p.n1;
-#pragma unroll
-  for (int k = 0; k < cdiv(kPipeChunks<T, R>, NW); ++k) {
-    const int c = wv + NW * k;  // wave-slot = item k of this wave (Window::item)
-    if (c < kPipeChunks<T, R>) {
-      int rl, gl, ru, gu;
-      (void)Window<T, R>::item(k, wv, ln, rl, gl, ru, gu);  // (idle lanes: clamped like the rest, dropped by pipe_window)
-      const int r = rl + ru, g = gl + gu;
-      int gr = ty0 - 2 * R + r, gc = tx0 - L::CA + V * g;
-      gr = gr < 0 ? 0 : gr >= n0 ? n0 - 1 : gr;
-      gc = gc < 0 ? 0 : gc > n1 - V ? n1 - V : gc;
-      const int64_t off = (int64_t)gr * n1 + gc;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xs + off),
-                                       (__attribute__((address_space(3))) void*)(raw + (size_t)c * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xps + off),
-                                       (__attribute__((address_space(3))) void*)(raw + kPipeArr<T, R> + (size_t)c * 1024),
-                                       16, 0, 0);
-    }
-  }
-}
-
-// staged window -> yk in A (and the window partials), behind a barrier after every wave's pieces have landed
-template <typename T, int R>
-__device__ inline void pipe_window(const PgdParams<T>& p, T* A, const unsigned char* raw, int ty0, int tx0,
-                                   double* __restrict__ partials, unsigned tile, const int tid) {
-  using L = Layout<T, R>;
-  constexpr int V = L::V;
-  const int n0 = p.n0, n1 = p.n1;
-  const T* rx = reinterpret_cast<const T*>(raw);
-  const T* rp = reinterpret_cast<const T*>(raw + kPipeArr<T, R>);
-  Window<T, R> w;
-  int wv, ln;
-  wave_lane(tid, wv, ln);
-#pragma unroll
-  for (int k = 0; k < Window<T, R>::K0; ++k) {
-    const int it = tid + k * kThreads;  // staged vector of wave-slot wv + NW k, lane ln
-    int rl, gl, ru, gu;
-    if (Window<T, R>::item(k, wv, ln, rl, gl, ru, gu)) {
-      const int gr = ty0 - 2 * R + rl + ru, gc = tx0 - L::CA + V * (gl + gu);
-      ld_vec<T, V>(rx + V * it, w.xv[k]);
-      ld_vec<T, V>(rp + V * it, w.pv[k]);
-      if (!(gr >= 0 && gr < n0 && gc >= 0 && gc < n1)) {
-#pragma unroll
-        for (int v = 0; v < V; ++v) w.xv[k][v] = w.pv[k][v] = T(0);
-      }
-    }
-  }
-  win_store<T, R>(p, A, w, tid);
-  if (p.win_part && partials != nullptr) win_partials<T, R>(w, partials, tile, tid);
-}
-
-template <typename T, int R>
-__global__ void __launch_bounds__(kThreads, 2) pgd_pipe_kernel(PgdParams<T> p, const T* __restrict__ x,
-                                                            const T* __restrict__ xp, const T* __restrict__ b,
-                                                            T* __restrict__ xn, double* __restrict__ partials) {
-  using L = Layout<T, R>;
-  extern __shared__ __align__(16) unsigned char smem_raw[];
-  const unsigned nw = p.pipe_wgs;
-  if (p.pub_src != nullptr && blockIdx.x == nw) {  // the publishing workgroup (its reduction area: the carve's start)
-    publish_prev<T>(p, reinterpret_cast<double*>(smem_raw));
-    return;
-  }
-  T* A = reinterpret_cast<T*>(smem_raw);
-  T* KT = A + L::AR * L::AP + L::AC * L::PTP;
-  unsigned char* raw = smem_raw + kPipeRawOff<T, R>;
-  const int tid = threadIdx.x;
-  if (tid < 2 * R + 1) {
-    KT[tid] = p.k0[tid];
-    KT[kKT + tid] = p.k1[tid];
-  }
-  const unsigned tpi = (unsigned)p.tiles0 * (unsigned)p.tiles1;
-  const int64_t img = (int64_t)p.n0 * p.n1;
-  // virtual block index -> (tile, image, tile origin), as the tile kernel maps its block index (XCD band, the last
-  // band backwards)
-  auto locate = [&](unsigned i, unsigned& tile, unsigned& si, int& ty0, int& tx0) {
-    tile = xcd_tile(i, p.ntiles);
-    const unsigned nb = p.ntiles, q8 = nb >> 3, r8 = nb & 7u, g8 = i & 7u;
-    if (g8 == 7u) {
-      const unsigned lo = 7u * q8 + (r8 < 7u ? r8 : 7u), len = q8 + (7u < r8 ? 1u : 0u);
-      tile = lo + (len - 1u - (tile - lo));
-    }
-    si = tile / tpi;
-    const unsigned tr = tile - si * tpi, trow = tr / (unsigned)p.tiles1;
-    ty0 = (int)trow * TY;
-    tx0 = (int)(tr - trow * (unsigned)p.tiles1) * TX;
-  };
-  unsigned i = blockIdx.x, tile, si;
-  int ty0, tx0;
-  locate(i, tile, si, ty0, tx0);
-  pipe_issue<T, R>(p, raw, ty0, tx0, x + (int64_t)si * img, xp + (int64_t)si * img, tid);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  body_sync<true>();
-  pipe_window<T, R>(p, A, raw, ty0, tx0, partials, tile, tid);
-  using KP = const __attribute__((address_space(4))) PgdParams<T>*;
-  for (;;) {
-    // the parameters re-read (scalar loads from the kernel-argument segment) per tile: hoisted out of the loop, the
-    // taps and geometry stay live across it and spill
-    KP kp = (KP)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(kp));
-    const PgdParams<T>& p = *(const PgdParams<T>*)kp;
-    body_sync<true>();  // A holds this tile's window; the staging area is free
-    const unsigned inext = i + nw;
-    const bool more = inext < p.ntiles;
-    unsigned tile_n = 0, si_n = 0;
-    int ty0n = 0, tx0n = 0;
-    if (more) {
-      locate(inext, tile_n, si_n, ty0n, tx0n);
-      pipe_issue<T, R>(p, raw, ty0n, tx0n, x + (int64_t)si_n * img, xp + (int64_t)si_n * img, tid);
-    }
-    const T* bs = b + (int64_t)(si % (unsigned)p.y_images) * img;
-    T* xns = xn + (int64_t)si * img;
-    const T* xrs = (p.xref != nullptr ? p.xref : x) + (int64_t)si * img;
-    const bool interior = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 && tx0 - L::CA >= 0 &&
-                          tx0 + TX + L::CA <= p.n1;
-    double* bp = p.win_part ? nullptr : partials;
-    if (interior)
-      pgd_tile_body<T, R, false, PXA_PGD_SWEEP_DEPTH, true>(p, smem_raw, tile, ty0, tx0, bs, xns, bp, xrs, nullptr,
-                                                            NoHook{}, tid);
-    else
-      pgd_tile_body<T, R, true, PXA_PGD_SWEEP_DEPTH, true>(p, smem_raw, tile, ty0, tx0, bs, xns, bp, xrs, nullptr,
-                                                           NoHook{}, tid);
-    if (!more) break;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pieces of the next window have landed
-    body_sync<true>();                                 // ... every wave's, and every read of A by this tile is done
-    pipe_window<T, R>(p, A, raw, ty0n, tx0n, partials, tile_n, tid);
-    i = inext;
-    tile = tile_n;
-    si = si_n;
-    ty0 = ty0n;
-    tx0 = tx0n;
-  }
-}
-
-// resident workgroups per CU of the pipelined kernel, and the CU count of the current device (cached per device)
-constexpr int kPipePerCu = 2;
-inline int device_cus() {
-  static int cus[64] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-  if (cus[dev] == 0) {
-    int n = 0;
-    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    cus[dev] = n;
-  }
-  return cus[dev];
-}
-
-template <typename T, int R>
-int launch_pgd_pipe(const PgdParams<T>& p, const void* x, const void* xp, const void* b, void* xn, double* partials,
-                    hipStream_t s) {
-  const size_t smem = kPipeBytes<T, R>;
-  auto kern = pgd_pipe_kernel<T, R>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_set = true;
-  }
-  hipLaunchKernelGGL(kern, dim3(p.pipe_wgs + (p.pub_src != nullptr ? 1u : 0u)), dim3(kThreads), smem, s, p, (const T*)x,
-                     (const T*)xp, (const T*)b, (T*)xn, partials);
-  return last_launch_status();
-}
-
 template <typename T, int R>
 int launch_pgd(const PgdParams<T>& p, const void* x, const void* xp, const void* b, void* xn, double* partials,
                hipStream_t s) {
-  constexpr bool strip_fits = kStripXOff<T, R> + kStripXBytes <= (size_t)160 * 1024;  // (fp64 at large R: no)
-  constexpr bool pipe_fits = sizeof(T) == 4 && kPipeBytes<T, R> * kPipePerCu <= (size_t)160 * 1024;
-  if (pipe_fits && p.pipe_wgs > 0) {
-    const int e = launch_pgd_pipe<T, R>(p, x, xp, b, xn, partials, s);
-    if (e == PXA_OK) g_last_pgd_kernel = 3;
-    return e;
-  }
-  if (strip_fits && p.slen >= 2) {
-    const int e = launch_pgd_strip<T, R>(p, x, xp, b, xn, partials, s);
-    if (e == PXA_OK) g_last_pgd_kernel = 2;
-    return e;
-  }
   g_last_pgd_kernel = 1;
   // Layout + the ghost terms (+ the timing trace under PXA_TUNE_PGD_DIAG bit 5)
   const size_t smem = kGhOff<T, R> + kGhBytes<T, R> + ((p.diag & 32) ? 256 : 0);
@@ -1450,7 +1023,6 @@ int pgd_params(int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0,
   p.inv_mu = (T)(1.0 / mu);
   p.tv = lam != 0.0;
   p.prox = prox;
-  p.round1 = 4u * 256u;
   return PXA_OK;
 }
 
@@ -1471,7 +1043,6 @@ int pgd_run(PgdParams<T> p, int R, double a, double tau, double prox_w, const vo
              (x_ref == nullptr || aligned16(x_ref));
   p.xref = (partials != nullptr && x_ref != nullptr && x_ref != x) ? (const T*)x_ref : nullptr;
   p.diag = kProbes ? tuning(PXA_TUNE_PGD_DIAG) : 0;
-  p.stagger = kProbes ? tuning(PXA_TUNE_PGD_STAGGER) : 0;
   p.fold_vals = rel_values;
   p.fold_flags = (unsigned*)rel_flags;
   p.fold_seq = (unsigned)seq;
@@ -1487,29 +1058,6 @@ int pgd_run(PgdParams<T> p, int R, double a, double tau, double prox_w, const vo
   p.pub_vals = pub_vals;
   p.pub_flags = (unsigned*)pub_flags;
   p.pub_seq = (unsigned)pub_seq;
-  // kernel choice (PXA_TUNE_PGD_KERNEL): 0 / 1 the tile kernel (default); v >= 2 the strip kernel with strips of v
-  // tiles (A/B and tests: measured slower, see the strip kernel's comment)
-  {
-    const int64_t kv = tuning(PXA_TUNE_PGD_KERNEL);
-    int64_t sl = 1;
-    if (kv >= 2) sl = kv;
-    if (sl > p.tiles0) sl = p.tiles0;
-    if (sl < 1 || !p.vec_ok) sl = 1;  // (the strip kernel's row prefetch moves whole 16-B vectors only)
-    p.slen = (unsigned)sl;
-    p.sgroups = (unsigned)((p.tiles0 + sl - 1) / sl);
-    const int64_t ns = p.stack * (int64_t)p.sgroups * p.tiles1;
-    p.nstrips = (unsigned)ns;
-    if (ns > 0x7fffffff || win_part || pub_src) p.slen = 1;  // (window partials / publication: the tile kernel)
-    // PXA_TUNE_PGD_PIPE = 1: the pipelined kernel (whole 16-B vectors only; not with the last-workgroup fold)
-    p.pipe_wgs = 0;
-    if (tuning(PXA_TUNE_PGD_PIPE) == 1 && p.vec_ok && rel_values == nullptr) {
-      const unsigned cap = (unsigned)(kPipePerCu * device_cus());
-      unsigned nw = p.ntiles < cap ? p.ntiles : cap;
-      if (nw >= 8) nw -= nw % 8;  // a multiple of 8: every workgroup stays on its XCD's band
-      p.pipe_wgs = nw;
-      p.slen = 1;
-    }
-  }
   int st;
   switch (R) {
     case 1: st = launch_pgd<T, 1>(p, x, x_prev, hty, x_new, partials, s); break;

@@ -93,8 +93,8 @@ struct Pk<float> {
 // sweep and one V-vector across it, out[o][v] = sum_{t=0}^{4R} g[t] src[(o + t) * PS + v].
 // D = 0: the compiler schedules the NO + 4R row loads (it hoists most of them: ~4 VGPRs per row live at once).
 // D > 0: at most D rows in flight -- row j + D is loaded when row j is consumed, and a scheduling barrier (only
-// VALU / SALU may cross it) keeps the LDS reads in that order -- so a sweep holds ~4 (D + 1) row registers: the
-// PGD strip kernel's budget for its prefetched window rows.  Same FMAs in the same order: same bits.
+// VALU / SALU may cross it) keeps the LDS reads in that order -- so a sweep holds ~4 (D + 1) row registers (A/B
+// builds of the PGD tile kernel: PXA_PGD_SWEEP_DEPTH).  Same FMAs in the same order: same bits.
 template <typename T, int R, int NO, int PS, int D = 0>
 __device__ inline void sweep(const T* __restrict__ src, const T* __restrict__ g, T (&out)[NO][kVecN<T>]) {
   constexpr int V = kVecN<T>;

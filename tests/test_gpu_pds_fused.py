@@ -260,35 +260,55 @@ def test_pds_lookahead_two_positions_per_thread_bit_exact(algo):
         assert np.array_equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("dt", [np.float32, np.float64])
-@pytest.mark.parametrize("h_kind", ["l1", "iso"])
-@pytest.mark.parametrize("sh", [(67, 129), (9, 33, 70), (5, 64, 128)], ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("relax", [0, 1])
-def test_tv_dual_update_vs_oracle(dt, h_kind, sh, relax):
-    """pxa_tv_dual_update (kernel C alone, SURVEY §8(d) K4): relax(fenchel_prox_{sigma h}(z + sigma Grad w))
-    against the oracle's reference arithmetic (operator.py:905-944, diff.py:1113-1265; pds.py:760 / 441)."""
-    rng = np.random.default_rng(3)
-    N = int(np.prod(sh))
+UNIT = ([-1.0] * 3, [1.0] * 3)
+# a different forward-difference pair on every axis (sampling 0.7, 1.9, 1.3; D = 2 reads axes 1 and 2 only)
+PER_AXIS = ([-1 / 0.7, -1 / 1.9, -1 / 1.3], [1 / 0.7, 1 / 1.9, 1 / 1.3])
+PER_AXIS_SAMPLING = (0.7, 1.9, 1.3)
+
+
+def _dual_ref(w, z, sh, stack, per_axis, sigma, lam, rho, h_kind, relax):
+    """relax(fenchel_prox_{sigma h}(z + sigma Grad w)) in the oracle's reference arithmetic, per stack row."""
+    d = w.dtype.type
     Dd = len(sh)
-    w = rng.standard_normal(N).astype(dt)
-    z = (0.05 * rng.standard_normal(Dd * N)).astype(dt)
-    sigma, lam, rho = 0.37, 0.05, 0.7
-    geom = (1, 1, *sh, 2) if Dd == 2 else (1, *sh, 3)
-    out = to_NUMPY(_dev.tv_dual_update(D(w), D(z), geom, [-1.0] * 3, [1.0] * 3, sigma, lam, rho,
-                                       0 if h_kind == "l1" else 1, relax=relax))
-    d = np.dtype(dt).type
+    sampling = PER_AXIS_SAMPLING[3 - Dd:] if per_axis else 1.0
     if h_kind == "iso":
         hp = lambda v, t: orc.l21_prox(v, t * d(lam), (Dd, *sh))
     else:
         hp = lambda v, t: orc.l1_prox(v, t * d(lam))
-    zin = z + d(sigma) * orc.gradient_apply(w, arg_shape=sh)
-    zt = orc.fenchel_prox(hp, zin, sigma)
-    ref = (d(1 - rho) * z + d(rho) * zt) if relax == 0 else (d(rho) * zt + d(1 - rho) * z)
+    rows = []
+    for wr, zr in zip(w.reshape(stack, -1), z.reshape(stack, -1)):
+        zin = zr + d(sigma) * orc.gradient_apply(wr, arg_shape=sh, sampling=sampling)
+        zt = orc.fenchel_prox(hp, zin, sigma)
+        rows.append((d(1 - rho) * zr + d(rho) * zt) if relax == 0 else (d(rho) * zt + d(1 - rho) * zr))
+    return np.concatenate(rows)
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64])
+@pytest.mark.parametrize("h_kind", ["l1", "iso"])
+@pytest.mark.parametrize("sh,stack,coefs", [
+    pytest.param((67, 129), 1, UNIT, id="67x129"), pytest.param((9, 33, 70), 1, UNIT, id="9x33x70"),
+    pytest.param((5, 64, 128), 1, UNIT, id="5x64x128"),
+    # odd row counts, partial column blocks, a single row, stacks
+    pytest.param((7, 37, 1024), 1, UNIT, id="7x37x1024"), pytest.param((3, 1, 64), 2, UNIT, id="3x1x64-s2"),
+    pytest.param((6, 19, 260), 2, UNIT, id="6x19x260-s2"), pytest.param((5, 64, 128), 3, UNIT, id="5x64x128-s3"),
+    pytest.param((9, 33, 70), 1, PER_AXIS, id="9x33x70-per_axis"),
+    pytest.param((67, 129), 1, PER_AXIS, id="67x129-per_axis")])
+@pytest.mark.parametrize("relax", [0, 1])
+def test_tv_dual_update_vs_oracle(dt, h_kind, sh, stack, coefs, relax):
+    """pxa_tv_dual_update (kernel C alone, SURVEY §8(d) K4): relax(fenchel_prox_{sigma h}(z + sigma Grad w))
+    against the oracle's reference arithmetic (operator.py:905-944, diff.py:1113-1265; pds.py:760 / 441): 2-D and
+    3-D, stacks, unit and per-axis sampling."""
+    rng = np.random.default_rng(3)
+    N = int(np.prod(sh))
+    Dd = len(sh)
+    w = rng.standard_normal(stack * N).astype(dt)
+    z = (0.05 * rng.standard_normal(stack * Dd * N)).astype(dt)
+    sigma, lam, rho = 0.37, 0.05, 0.7
+    geom = (stack, 1, *sh, 2) if Dd == 2 else (stack, *sh, 3)
+    out = to_NUMPY(_dev.tv_dual_update(D(w), D(z), geom, *coefs, sigma, lam, rho,
+                                       0 if h_kind == "l1" else 1, relax=relax))
+    ref = _dual_ref(w, z, sh, stack, coefs is PER_AXIS, sigma, lam, rho, h_kind, relax)
     assert rel_err(out, ref) <= TOL[dt], rel_err(out, ref)
-
-
-UNIT = ([-1.0] * 3, [1.0] * 3)
-PER_AXIS = ([-1 / 0.7, -1 / 1.9, -1 / 1.3], [1 / 0.7, 1 / 1.9, 1 / 1.3])
 
 
 @pytest.mark.parametrize("rows", [1, 2, 4, 8, 9])

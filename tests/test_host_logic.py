@@ -51,6 +51,21 @@ def test_argument_validation_without_gpu():
     assert lib.pxa_pgd_tv2d_step(0, 1, 1, 8, 8, 0, None, None, 0, None, None, 1, 1, 0, 1, 0, 1, 0, 0, 1, 2, 3, 4, None, None, None) == -1
 
 
+def test_retired_tuning_keys_are_rejected():
+    # the knobs of the removed kernel variants fail loudly (PXA_ERR_ARG), set or read; a live key still works
+    lib = pyxu_amd.lib
+    for key in (0, 6, 12):
+        assert lib.pxa_tuning(key, 1) == -1
+        assert lib.pxa_tuning(key, -1) == -1
+    prev = lib.pxa_tuning(5, 1)  # PXA_TUNE_PDS_EVENTS
+    try:
+        assert lib.pxa_tuning(5, -1) == 1
+        assert lib.pxa_tuning(5, 0) == 1
+        assert lib.pxa_tuning(5, -1) == 0
+    finally:
+        lib.pxa_tuning(5, prev)
+
+
 @pytest.mark.parametrize("name", golden_names("gaussian_"))
 def test_gaussian_taps_match_reference(name):
     g = load_golden(name)
