@@ -14,8 +14,6 @@
  *       * pxa_pgd_tv2d_plan() allocates the plan's 4-byte device counter (released by
  *         pxa_pgd_tv2d_plan_free()); call it before a capture, then capture pxa_pgd_tv2d_plan_step();
  *       * pxa_host_alloc() / pxa_host_free() allocate / release coherent host memory (their purpose);
- *       * pxa_tuning(PXA_TUNE_PDS_MARCH, bit 2), the opt-in coupled kernel-D variant of A/B runs,
- *         allocates its progress counters on first use;
  *       * pxa_pds_kernel_ms() and pxa_pgd_tile_trace() (measurement hooks) wait for recorded events /
  *         copy a device symbol to the host;
  *   - `stream` is a hipStream_t (NULL = legacy default stream); launches are asynchronous;
@@ -58,9 +56,11 @@ extern "C" {
 #define PXA_MODE_SYMMETRIC 3
 #define PXA_MODE_EDGE 4
 
-/* Kernel-selection knobs (pxa_tuning).  Keys 0, 6 and 12 are retired (they selected the strip kernel, the
- * staggered-start probe and the pipelined kernel of the fused PGD step, all removed after losing their A/B
- * measurements): pxa_tuning returns PXA_ERR_ARG for them, and the numbers are not reused. */
+/* Kernel-selection knobs (pxa_tuning).  Keys 0, 6, 7 and 12 are retired: 0, 6 and 12 selected the strip
+ * kernel, the staggered-start probe and the pipelined kernel of the fused PGD step, 7 the variants of
+ * pxa_pds_step_la's kernel D (two positions per thread, persistent grid, progress coupling, no / deeper plane
+ * prefetch), all removed after losing their A/B measurements.  pxa_tuning returns PXA_ERR_ARG for them, and the
+ * numbers are not reused. */
 #define PXA_TUNE_NORMAL_KERNEL 1 /* A/B of pxa_dense_normal: 0 row-split kernel (each row in four column parts,
                                     one workgroup each, part-dots exchanged), 1 one workgroup per row (results
                                     equal up to summation order), 2 the row-split kernel computing every part-dot
@@ -76,13 +76,6 @@ extern "C" {
                               bit 9 the H^T y loads, bit 10 the x_new stores (scripts/pgd_modes_probe.py diag) */
 #define PXA_TUNE_PDS_EVENTS 5 /* measurement hook: > 0 makes pxa_pds_step record HIP events around each
                                  of its kernels (pxa_pds_kernel_ms) */
-#define PXA_TUNE_PDS_MARCH 7 /* A/B of pxa_pds_step_la's kernel D: bit 0 lets a thread own two positions
-                                (default one); bit 1 a persistent grid of the resident capacity (default one
-                                workgroup per unit); bit 2 a soft progress coupling of row-neighbour workgroups
-                                (fp32, radius 6: each waits, boundedly, while a started neighbour lags more than
-                                2 + (value >> 3) planes); bit 8 the march without its plane prefetch (the default
-                                issues every load of plane q + 1 before plane q is computed), bit 9 two planes
-                                ahead; same bits */
 #define PXA_TUNE_FFT_KERNEL 8 /* A/B of the in-LDS FFT (pxa_fft, lines that fit one workgroup): 0 in-place register-staged
                                  stages on padded lines with a twiddle table, 1 the ping-pong Stockham kernel of rounds
                                  1-3 (results equal up to rounding); bits 256 / 512 force 512- / 1024-thread

@@ -213,12 +213,11 @@ TUNE_DENSE_KERNEL = 2  # PXA_TUNE_DENSE_KERNEL: 0 LDS-staged MFMA GEMM (B >= 32)
 TUNE_DUAL_WGS = 4  # PXA_TUNE_DUAL_WGS: kernel C's target workgroup count (A/B; 0 = default)
 TUNE_PGD_DIAG = 3  # PXA_TUNE_PGD_DIAG: bit 5 = s_memtime phase trace of the PGD tile kernel
 TUNE_PDS_EVENTS = 5  # PXA_TUNE_PDS_EVENTS: per-kernel HIP events inside pxa_pds_step (pds_kernel_ms)
-TUNE_PDS_MARCH = 7  # PXA_TUNE_PDS_MARCH: kernel D A/B (bit 0: two positions per thread)
 TUNE_FFT_KERNEL = 8  # PXA_TUNE_FFT_KERNEL: 0 in-place register-staged FFT kernel, 1 the ping-pong Stockham kernel
 TUNE_GRAD_KERNEL = 9  # PXA_TUNE_GRAD_KERNEL: 0 axis-0 march gradient kernels, 1 the row kernels (same bits)
 TUNE_STENCIL_ND = 10  # PXA_TUNE_STENCIL_ND: 0 LDS-tiled N-D stencil where it applies, 1 the generic kernel (same sums)
 TUNE_DUAL_ROWS = 11  # PXA_TUNE_DUAL_ROWS: kernel C rows per thread (0 / 1 one-row kernel, 2 or 4 row-blocked; same bits)
-# (keys 0, 6, 12 are retired: pxa_tuning rejects them)
+# (keys 0, 6, 7, 12 are retired: pxa_tuning rejects them)
 
 
 def tuning(key, value=-1):

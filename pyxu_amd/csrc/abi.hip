@@ -26,7 +26,7 @@ const char* pxa_error_string(int code) {
 static int g_tuning[PXA_TUNE_COUNT] = {0};
 
 // keys whose kernel variants were removed (pyxu_amd.h): an error, so that a stale A/B script does not time the default
-static bool retired_key(int key) { return key == 0 || key == 6 || key == 12; }
+static bool retired_key(int key) { return key == 0 || key == 6 || key == 7 || key == 12; }
 
 int pxa_tuning(int key, int value) {
   if (key < 0 || key >= PXA_TUNE_COUNT || retired_key(key)) return PXA_ERR_ARG;
@@ -37,28 +37,6 @@ int pxa_tuning(int key, int value) {
 
 }  // extern "C"
 
-#include <map>
-#include <mutex>
-#include <tuple>
-
 namespace pxa {
 int tuning(int key) { return (key >= 0 && key < PXA_TUNE_COUNT) ? g_tuning[key] : 0; }
-
-int resident_grid(const void* kernel, int threads, size_t lds) {
-  static std::mutex mu;
-  static std::map<std::tuple<const void*, int, int, size_t>, int> cache;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  const auto key = std::make_tuple(kernel, dev, threads, lds);
-  std::lock_guard<std::mutex> lock(mu);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int cus = 0, per = 0;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kernel, threads, lds);
-  int g = cus * (per > 0 ? per : 1) / 8 * 8;
-  if (g < 8) g = 8;
-  cache[key] = g;
-  return g;
-}
 }  // namespace pxa

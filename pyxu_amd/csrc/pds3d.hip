@@ -42,37 +42,10 @@
 //
 // Parity: the step follows the reference's arithmetic per voxel except that G x replaces
 // S^T (S x - y) + ... (same operator, different fp32 rounding order: see pgd_tv2d.hip).
-#include <atomic>
-#include <map>
-#include <mutex>
-
 #include "pds_march.hpp"
 
 namespace pxa {
 namespace pds {
-
-// kernel D's soft-coupling counters (pds_march.hpp): per device, grown on demand, zeroed once
-unsigned* progress_counters(int64_t units) {
-  static std::mutex mu;
-  static std::map<int, std::pair<unsigned*, int64_t>> bufs;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  auto& b = bufs[dev];
-  if (b.second < units) {
-    unsigned* p = nullptr;
-    if (hipMalloc((void**)&p, (size_t)units * sizeof(unsigned)) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, (size_t)units * sizeof(unsigned)) != hipSuccess) return nullptr;
-    // (the previous, smaller buffer stays allocated: a kernel still in flight may use it)
-    b = {p, units};
-  }
-  return b.first;
-}
-
-unsigned next_progress_tag() {
-  static std::atomic<unsigned> n{0};
-  return ((n.fetch_add(1) % 65535u) + 1u) << 16;
-}
 
 // ------------------------------------------------------------------ kernel C: dual update
 template <typename T>
@@ -962,7 +935,6 @@ int pds_la_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int3
   PXA_CHECK_ARG(x && z && hty && z_out && work_w && x_out && x_out != x && z_out != z);
   PXA_CHECK_ARG(pd3o ? (u && u_out) : (work_kt != nullptr));
   if (!S.id0) PXA_CHECK_ARG(work_q != nullptr);
-  const PdsGeom<T>& g = S.g;
   const int64_t M = S.M;
   PdsD<T> pd;
   pd.a = make_a(S, nseg);
@@ -970,18 +942,13 @@ int pds_la_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int3
   pd.lam = S.lam;
   pd.rho = S.rho;
   pd.omr = S.omr;
-  // kernel D's per-thread pairs: even rows and 8-byte aligned streams
-  auto a2 = [](const void* p) { return p == nullptr || (uintptr_t)p % (2 * sizeof(T)) == 0; };
-  const bool np2 = (g.n2 % 2 == 0) && a2(x) && a2(u) && a2(z) && a2(x_out) && a2(u_out) && a2(z_out) &&
-                   a2(work_q) && a2(work_kt) && a2(work_w);
-  const int np = np2 ? 2 : 1;
   // q is written only when axis 0 is blurred; kernel B then reads it, else v itself
   void* q = S.id0 ? work_w : work_q;
 
   const bool evs = tuning(PXA_TUNE_PDS_EVENTS) > 0;
   if (evs) pds_event(0, st);
   if (!primed) {  // the march of this iteration: v from (u or x, z) without a dual update
-    const int e = run_d(pd, pd3o, S.iso, false, S.R0, np, M, nseg, work_w, z, pd3o ? u : x, z_out,
+    const int e = run_d(pd, pd3o, S.iso, false, S.R0, M, nseg, work_w, z, pd3o ? u : x, z_out,
                         pd3o ? x : work_kt, q, st);
     if (e) return e;
   }
@@ -995,7 +962,7 @@ int pds_la_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int3
   if (evs) pds_event(2, st);
   {
     // dual update of this iteration + the next iteration's march
-    const int e = run_d(pd, pd3o, S.iso, true, S.R0, np, M, nseg, work_w, z, pd3o ? (const void*)u_out : x_out,
+    const int e = run_d(pd, pd3o, S.iso, true, S.R0, M, nseg, work_w, z, pd3o ? (const void*)u_out : x_out,
                         z_out, pd3o ? x_out : work_kt, q, st);
     if (e) return e;
   }

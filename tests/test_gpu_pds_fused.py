@@ -174,7 +174,13 @@ def test_pds_fused_stacked_rows_and_no_input_mutation(algo):
             assert rel_err(xs[r], to_NUMPY(s1._mstate["x"])) <= 1e-6
 
 
-LA_CASES = [c for i, c in enumerate(CASES) if i in (0, 1, 2, 4, 5, 6)]
+LA_CASES = [c for i, c in enumerate(CASES) if i in (0, 1, 2, 4, 5, 6)] + [
+    # kernel D's in-plane layout with isotropic TV and a prox: 256-position blocks that straddle rows; rows wider
+    # than one block (the column - 1 neighbour crosses a block boundary).  Neither is deep enough for automatic
+    # segments at radius 6: test_pds_lookahead_segments_bit_exact, ..._segments_wide_rows_bit_exact force them
+    ((17, 40, 70), 2.0, "iso", "pos", np.float32, False),
+    ((24, 128, 512), 2.0, "iso", "pos", np.float32, False),
+]
 
 
 def _run(algo, case, n, lookahead, x0, interrupt=None):
@@ -219,10 +225,8 @@ def test_pds_lookahead_reprimes_after_state_change(algo):
         assert np.array_equal(a[k], b[k]), k
 
 
-@pytest.mark.parametrize("algo", [0, 1])
-def test_pds_lookahead_segments_bit_exact(algo):
-    """Kernel D's axis-0 segments recompute their halo planes (z, K^T z, v) with the same arithmetic."""
-    sh = (37, 40, 64)
+def _la_segments(algo, sh, nsegs):
+    """Outputs of one un-primed pxa_pds_step_la per segment count must agree bit for bit."""
     N = int(np.prod(sh))
     x0 = np.random.default_rng(3).uniform(0, 1, N).astype(np.float32)
     with pxrt.Precision(pxrt.Width.SINGLE):
@@ -231,7 +235,7 @@ def test_pds_lookahead_segments_bit_exact(algo):
         s.fit(x0=D(x0), stop_crit=pxst.MaxIter(3))
         p, m = s._plan, s._mstate
         outs = []
-        for nseg in (1, 3, 37):
+        for nseg in nsegs:
             x = _dev.copy(m["x"])
             u = _dev.copy(m["u"]) if algo == 0 else None
             xo, zo = _dev.empty_like(m["x"]), _dev.empty_like(m["z"])
@@ -245,19 +249,17 @@ def test_pds_lookahead_segments_bit_exact(algo):
             assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("algo", ["pd3o", "cv"])
-def test_pds_lookahead_two_positions_per_thread_bit_exact(algo):
-    """Kernel D with two positions per thread (PXA_TUNE_PDS_MARCH bit 0) gives the default's bits."""
-    case = ((17, 40, 70), 2.0, "iso", "pos", np.float32, False)
-    x0 = np.random.default_rng(7).uniform(0, 1, int(np.prod(case[0]))).astype(np.float32)
-    a = _run(algo, case, 4, True, x0)
-    prev = _dev.tuning(_dev.TUNE_PDS_MARCH, 1)
-    try:
-        b = _run(algo, case, 4, True, x0)
-    finally:
-        _dev.tuning(_dev.TUNE_PDS_MARCH, prev)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
+@pytest.mark.parametrize("algo", [0, 1])
+def test_pds_lookahead_segments_bit_exact(algo):
+    """Kernel D's axis-0 segments recompute their halo planes (z, K^T z, v) with the same arithmetic."""
+    _la_segments(algo, (37, 40, 64), (1, 3, 37))
+
+
+@pytest.mark.parametrize("algo", [0, 1])
+def test_pds_lookahead_segments_wide_rows_bit_exact(algo):
+    """The same on rows wider than one 256-position block (520 columns: the column - 1 neighbour of a block's first
+    position belongs to another workgroup), with segments shorter than the 2 R0 = 12 halo planes."""
+    _la_segments(algo, (26, 6, 520), (1, 2, 5))
 
 
 UNIT = ([-1.0] * 3, [1.0] * 3)
@@ -342,62 +344,3 @@ def test_tv_dual_update_row_blocked_bit_exact(rows, dt, h_kind, sh, stack, coefs
         finally:
             _dev.tuning(_dev.TUNE_DUAL_ROWS, prev)
         assert np.array_equal(got, ref), (relax, rows)
-
-
-@pytest.mark.parametrize("algo", ["pd3o", "cv"])
-def test_pds_lookahead_persistent_grid_bit_exact(algo):
-    """Kernel D on a persistent grid (PXA_TUNE_PDS_MARCH bit 1: workgroups loop over the (segment, block) units)
-    gives the one-workgroup-per-unit launch's bits.  512 in-plane blocks x the automatic segments: more units
-    than resident workgroups, so the workgroups do loop."""
-    case = ((40, 256, 512), 2.0, "iso", "pos", np.float32, False)
-    x0 = np.random.default_rng(8).uniform(0, 1, int(np.prod(case[0]))).astype(np.float32)
-    a = _run(algo, case, 4, True, x0)
-    prev = _dev.tuning(_dev.TUNE_PDS_MARCH, 2)
-    try:
-        b = _run(algo, case, 4, True, x0)
-    finally:
-        _dev.tuning(_dev.TUNE_PDS_MARCH, prev)
-    for k in a:
-        assert np.array_equal(a[k], b[k]), k
-
-
-@pytest.mark.parametrize("algo", ["pd3o", "cv"])
-@pytest.mark.parametrize("slack", [0, 8])
-def test_pds_lookahead_coupled_march_bit_exact(algo, slack):
-    """Kernel D with the soft progress coupling of row neighbours (PXA_TUNE_PDS_MARCH bit 2; bits 3+ widen the
-    allowed lag) gives the default launch's bits: the coupling only delays workgroups, it never changes what
-    they compute.  256-wide rows (one block per row) and 512-wide ones (two), more units than resident
-    workgroups, so some neighbours are not resident when others wait for them (the bounded spin)."""
-    for shape in ((40, 256, 256), (24, 128, 512)):
-        case = (shape, 2.0, "iso", "pos", np.float32, False)
-        x0 = np.random.default_rng(9).uniform(0, 1, int(np.prod(shape))).astype(np.float32)
-        a = _run(algo, case, 4, True, x0)
-        prev = _dev.tuning(_dev.TUNE_PDS_MARCH, 4 | (slack << 3))
-        try:
-            b = _run(algo, case, 4, True, x0)
-        finally:
-            _dev.tuning(_dev.TUNE_PDS_MARCH, prev)
-        for k in a:
-            assert np.array_equal(a[k], b[k]), (shape, k)
-
-
-@pytest.mark.parametrize("algo", ["pd3o", "cv"])
-@pytest.mark.parametrize("case", LA_CASES + [((40, 256, 512), 2.0, "iso", "pos", np.float32, False)],
-                         ids=lambda c: "x".join(map(str, c[0])) + f"-{c[2]}-{np.dtype(c[4]).name}" if isinstance(c, tuple) else str(c))
-def test_pds_lookahead_prefetch_march_bit_exact(algo, case):
-    """Kernel D with every load of plane q + 1 issued before plane q is computed (the default: two planes of loads in
-    flight per wave; PXA_TUNE_PDS_MARCH bit 9: three) gives the bits of the march without prefetch (bit 8): 2-D / 3-D,
-    iso / aniso, fp32 / fp64, batch-as-axis."""
-    N = int(np.prod(case[0]))
-    x0 = np.random.default_rng(9).uniform(0, 1, N).astype(case[4])
-    a = _run(algo, case, 5, True, x0)
-    res = {}
-    for v in (256, 512):
-        prev = _dev.tuning(_dev.TUNE_PDS_MARCH, v)
-        try:
-            res[v] = _run(algo, case, 5, True, x0)
-        finally:
-            _dev.tuning(_dev.TUNE_PDS_MARCH, prev)
-    for v, b in res.items():
-        for k in a:
-            assert np.array_equal(a[k], b[k]), (v, k)

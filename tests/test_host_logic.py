@@ -54,7 +54,7 @@ def test_argument_validation_without_gpu():
 def test_retired_tuning_keys_are_rejected():
     # the knobs of the removed kernel variants fail loudly (PXA_ERR_ARG), set or read; a live key still works
     lib = pyxu_amd.lib
-    for key in (0, 6, 12):
+    for key in (0, 6, 7, 12):
         assert lib.pxa_tuning(key, 1) == -1
         assert lib.pxa_tuning(key, -1) == -1
     prev = lib.pxa_tuning(5, 1)  # PXA_TUNE_PDS_EVENTS
