@@ -599,6 +599,26 @@ int pxa_real_to_complex(int dtype, int64_t n, const void* x, void* z, void* stre
 /* x[i] = Re z[i] (FFT(real=True).adjoint output, fft.py:370-379); n complex elements. */
 int pxa_complex_real_part(int dtype, int64_t n, const void* z, void* x, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Non-uniform DFT by direct evaluation (operator/linop/fft/nufft.py:2820-2880, what NUFFT.type1/2/3
+ * compute with eps = 0):
+ *   out[q, n] = sum_m w[q, m] exp(i isign <src_m, tgt_n>),   isign = +1 / -1
+ * src (M, D) and tgt (N, D) real coordinates, D in {1, 2, 3}; w (Q, M) and out (Q, N) interleaved
+ * complex.  A workgroup owns tile_n targets and stages tile_m sources at a time through LDS; the sine /
+ * cosine of a (source, target) pair is shared by q_chunk stack rows, and a larger stack runs in passes.
+ * The grid is target tiles x source splits: `splits` = 0 lets the library choose from (M, N) alone (more
+ * than one only when the target tiles do not fill the chip), `splits` >= 1 (<= 65535) forces the count.
+ * Split s owns sources [s Ms, (s + 1) Ms), Ms = ceil(M / splits); with more than one split the partials go
+ * to `work` and a second launch adds them in ascending split order.  No atomics: the same call gives the
+ * same bits, and splits = 0 gives the bits of the count it resolves to.  M = 0 gives out = 0.
+ * pxa_nudft_workspace_bytes: splits_resolved * Q * N complex elements when splits_resolved > 1, else 0
+ * (so the resolved count can be read off it); (size_t)-1 for arguments outside the envelope.
+ * ------------------------------------------------------------------------------------------- */
+int pxa_nudft_tiles(int dtype, int64_t* tile_n, int64_t* tile_m, int64_t* q_chunk);
+size_t pxa_nudft_workspace_bytes(int dtype, int D, int64_t Q, int64_t M, int64_t N, int64_t splits);
+int pxa_nudft(int dtype, int D, int64_t Q, int64_t M, int64_t N, const void* src, const void* tgt, int isign,
+              const void* w, void* out, int64_t splits, void* work, void* stream);
+
 /* Measurement hook: with pxa_tuning(PXA_TUNE_PDS_EVENTS, 1), pxa_pds_step / pxa_pds_step_la record HIP
  * events around their kernels (at most 64 steps).  This call waits for the last of them and writes into
  * ms_abc[3] the summed durations of kernels A (axis-0 march; the look-ahead step's priming march, 0 when

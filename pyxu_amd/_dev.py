@@ -1391,4 +1391,41 @@ def complex_mul(a, b, conj_b=False, out=None):
     return out
 
 
+# ------------------------------------------------------------------ NUDFT
+def nudft_tiles(dtype_code):
+    """(tile_n, tile_m, q_chunk) of pxa_nudft: targets per workgroup, sources per LDS tile, stack rows per pass."""
+    v = [ct.c_int64(0) for _ in range(3)]
+    check(lib.pxa_nudft_tiles(int(dtype_code), *[ct.byref(a) for a in v]), "pxa_nudft_tiles")
+    return tuple(int(a.value) for a in v)
+
+
+def nudft_splits(dtype_code, D, Q, M, N, splits=0):
+    """Source splits pxa_nudft runs with for these shapes (`splits` = 0: the library's choice)."""
+    wsz = int(lib.pxa_nudft_workspace_bytes(int(dtype_code), int(D), int(Q), int(M), int(N), int(splits)))
+    if wsz == (1 << 64) - 1:
+        check(-3, "pxa_nudft_workspace_bytes")  # PXA_ERR_UNSUPPORTED
+    return 1 if wsz == 0 else wsz // (Q * N * 2 * (4 if dtype_code == 0 else 8))
+
+
+def nudft(src, tgt, isign, w, splits=0, out=None):
+    """out[q, n] = sum_m w[q, m] exp(i isign <src_m, tgt_n>) (pxa_nudft): src (M, D), tgt (N, D), w (Q, 2 M) and
+    out (Q, 2 N) interleaved complex."""
+    torch = _torch()
+    src, tgt, w = require(src, "src"), require(tgt, "tgt"), require(w, "w")
+    if not (src.dtype == tgt.dtype == w.dtype):
+        raise TypeError("pyxu_amd: nudft operands must share one dtype.")
+    (M, D), N, Q = src.shape, tgt.shape[0], w.shape[0]
+    if tgt.shape[1] != D or w.shape[1] != 2 * M:
+        raise ValueError(f"nudft: src {tuple(src.shape)}, tgt {tuple(tgt.shape)}, w {tuple(w.shape)} do not match.")
+    out = empty((Q, 2 * N), w) if out is None else out
+    dt = dtcode(w)
+    wsz = int(lib.pxa_nudft_workspace_bytes(dt, D, Q, M, N, int(splits)))
+    if wsz == (1 << 64) - 1:
+        check(-3, "pxa_nudft_workspace_bytes")  # PXA_ERR_UNSUPPORTED
+    work = torch.empty((wsz,), dtype=torch.uint8, device=w.device) if wsz > 0 else None
+    check(lib.pxa_nudft(dt, D, Q, M, N, ptr(src), ptr(tgt), int(isign), ptr(w), ptr(out), int(splits),
+                        ptr(work) if work is not None else None, stream()), "pxa_nudft")
+    return out
+
+
 _tuning_from_env()

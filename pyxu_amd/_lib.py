@@ -111,6 +111,9 @@ EXPORTS = {
     "pxa_complex_mul": (i32, [i32, i64, i64, vp, vp, i32, vp, vp]),
     "pxa_real_to_complex": (i32, [i32, i64, vp, vp, vp]),
     "pxa_complex_real_part": (i32, [i32, i64, vp, vp, vp]),
+    "pxa_nudft_tiles": (i32, [i32, P_i64, P_i64, P_i64]),
+    "pxa_nudft_workspace_bytes": (sz, [i32, i32, i64, i64, i64, i64]),
+    "pxa_nudft": (i32, [i32, i32, i64, i64, i64, vp, vp, i32, vp, vp, i64, vp, vp]),
     "pxa_pds_kernel_ms": (i32, [vp, i32]),
     "pxa_pds_step": (
         i32,
