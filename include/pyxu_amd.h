@@ -619,6 +619,41 @@ size_t pxa_nudft_workspace_bytes(int dtype, int D, int64_t Q, int64_t M, int64_t
 int pxa_nudft(int dtype, int D, int64_t Q, int64_t M, int64_t N, const void* src, const void* tgt, int isign,
               const void* w, void* out, int64_t splits, void* work, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gridding NUFFT, types 1 and 2 (what NUFFT.type1/2 compute with eps > 0): the kernels around pxa_fft_ex on
+ * the oversampled grid of nf[D] cells, D in {1, 2, 3}, with the kernel phi(z) = exp(beta (sqrt(1 - z^2) - 1))
+ * of w cells (2 <= w <= 16, nf[d] >= 2 w) per axis.  Type 1 is spread, FFT, deconv (to_grid = 0); type 2 is
+ * deconv (to_grid = 1), FFT, interp.  Interleaved complex everywhere; `grid` is (Q, nf[0], .., nf[D-1]).
+ *
+ * The plan comes from the host.  For point j (coordinate xi in fine-grid units, in [0, nf)) and axis d:
+ * l0 (M, D) int32, the first touched cell ceil(xi - w/2) (may be negative or >= nf; folded modulo nf), and
+ * off (M, D), xi - l0 in [w/2 - 1, w/2], both stored in the order of a stable sort of the points by bin;
+ * perm (M) maps a sorted position to the point's index in `c`; bin_start (nbins + 1) are the bins' offsets
+ * in that order.  A bin is a tile of bin_shape cells (pxa_nufft_grid_tiles), bins per axis
+ * ceil(nf / bin_shape), id row-major, and a point belongs to the bin of floor(xi).
+ *
+ * pxa_nufft_spread: grid[q, l] = sum_j c[q, j] prod_d phi(2 (l_d - xi_jd) / w), periodic.  One workgroup
+ *   owns one bin's cells for q_chunk stack rows and walks the sorted points of the bins within reach, `batch`
+ *   candidates at a time; every cell is written once (zeros included: `grid` needs no clearing), by plain
+ *   stores.  No atomics, no workspace: the same call gives the same bits.  c is (Q, M).
+ * pxa_nufft_interp: out[q, j] = sum_l grid[q, l] prod_d phi(..), the transpose: one thread per point, kernel
+ *   values computed once per point and shared by q_chunk rows, terms added in a fixed order.  out is (Q, M).
+ * pxa_nufft_deconv: n[D] modes per axis (n[d] <= nf[d]), corr the concatenated per-axis correction vectors
+ *   (sum n[d] values; entry k + n/2 belongs to mode k in [-(n/2), (n-1)/2]); modeord 0: modes ascending,
+ *   1: FFT order.  to_grid = 1: out (Q, nf..) = in (Q, n..) scaled, mode k in cell k mod nf, zero elsewhere;
+ *   to_grid = 0: out (Q, n..) = the modes' cells of in (Q, nf..), scaled.  No fftshift copy exists.
+ * None of them allocates or synchronises.  Q = 0 does nothing; M = 0 spreads zeros.
+ * ------------------------------------------------------------------------------------------- */
+int pxa_nufft_grid_tiles(int dtype, int D, int64_t* bin_shape /* [3] */, int64_t* q_chunk, int64_t* batch);
+int pxa_nufft_spread(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                     const int32_t* l0, const void* off, const int64_t* perm, const int64_t* bin_start,
+                     const void* c, void* grid, void* stream);
+int pxa_nufft_interp(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                     const int32_t* l0, const void* off, const int64_t* perm, const void* grid, void* out,
+                     void* stream);
+int pxa_nufft_deconv(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* nf, int modeord, int to_grid,
+                     const void* corr, const void* in, void* out, void* stream);
+
 /* Measurement hook: with pxa_tuning(PXA_TUNE_PDS_EVENTS, 1), pxa_pds_step / pxa_pds_step_la record HIP
  * events around their kernels (at most 64 steps).  This call waits for the last of them and writes into
  * ms_abc[3] the summed durations of kernels A (axis-0 march; the look-ahead step's priming march, 0 when

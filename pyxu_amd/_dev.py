@@ -1428,4 +1428,71 @@ def nudft(src, tgt, isign, w, splits=0, out=None):
     return out
 
 
+# ------------------------------------------------------------------ gridding NUFFT
+def nufft_grid_tiles(dtype_code, D):
+    """(bin_shape, q_chunk, batch) of the gridding kernels: fine-grid cells per bin along each of the D axes, stack
+    rows per workgroup, candidate points per batch of pxa_nufft_spread.  Needs no GPU."""
+    shape = (ct.c_int64 * 3)()
+    qc, batch = ct.c_int64(0), ct.c_int64(0)
+    check(lib.pxa_nufft_grid_tiles(int(dtype_code), int(D), shape, ct.byref(qc), ct.byref(batch)),
+          "pxa_nufft_grid_tiles")
+    return tuple(int(v) for v in shape[:int(D)]), int(qc.value), int(batch.value)
+
+
+def _nufft_plan_check(plan, name):
+    torch = _torch()
+    l0, off, perm, bin_start = plan
+    M, D = off.shape
+    if not (l0.dtype == torch.int32 and perm.dtype == torch.int64 and bin_start.dtype == torch.int64):
+        raise TypeError(f"{name}: l0 must be int32, perm and bin_start int64.")
+    if tuple(l0.shape) != (M, D) or perm.numel() != M or not all(a.is_cuda and a.is_contiguous() for a in plan):
+        raise ValueError(f"{name}: plan arrays do not match.")
+    return M, D
+
+
+def nufft_spread(nf, w, beta, plan, c, out=None):
+    """grid (Q, 2 prod nf) = spread of c (Q, 2 M) with the plan (l0, off, perm, bin_start) (pxa_nufft_spread)."""
+    c = require(c, "c")
+    M, D = _nufft_plan_check(plan, "nufft_spread")
+    l0, off, perm, bin_start = plan
+    Q = c.shape[0]
+    if len(nf) != D or c.shape[1] != 2 * M or off.dtype != c.dtype:
+        raise ValueError(f"nufft_spread: nf {tuple(nf)}, off {tuple(off.shape)}, c {tuple(c.shape)} do not match.")
+    nbins = int(np.prod([-(-int(f) // e) for f, e in zip(nf, nufft_grid_tiles(dtcode(c), D)[0])]))
+    if bin_start.numel() != nbins + 1:
+        raise ValueError(f"nufft_spread: bin_start has {bin_start.numel()} entries, the grid {nbins} bins.")
+    out = empty((Q, 2 * int(np.prod(nf))), c) if out is None else out
+    check(lib.pxa_nufft_spread(dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off), ptr(perm),
+                               ptr(bin_start), ptr(c), ptr(out), stream()), "pxa_nufft_spread")
+    return out
+
+
+def nufft_interp(nf, w, beta, plan, grid, out=None):
+    """out (Q, 2 M) = interpolation of grid (Q, 2 prod nf) at the plan's points (pxa_nufft_interp)."""
+    grid = require(grid, "grid")
+    M, D = _nufft_plan_check(plan, "nufft_interp")
+    l0, off, perm, _ = plan
+    Q = grid.shape[0]
+    if len(nf) != D or grid.shape[1] != 2 * int(np.prod(nf)) or off.dtype != grid.dtype:
+        raise ValueError(f"nufft_interp: nf {tuple(nf)}, off {tuple(off.shape)}, grid {tuple(grid.shape)} do not match.")
+    out = empty((Q, 2 * M), grid) if out is None else out
+    check(lib.pxa_nufft_interp(dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
+                               ptr(perm), ptr(grid), ptr(out), stream()), "pxa_nufft_interp")
+    return out
+
+
+def nufft_deconv(N, nf, modeord, to_grid, corr, z, out=None):
+    """to_grid: modes z (Q, 2 prod N) -> fine grid (Q, 2 prod nf), scaled by `corr` and zero-embedded; otherwise the
+    fine grid's N central modes, scaled (pxa_nufft_deconv).  `corr`: the concatenated per-axis correction vectors."""
+    z, corr = require(z, "z"), require(corr, "corr")
+    Q, n_in, n_out = z.shape[0], int(np.prod(N if to_grid else nf)), int(np.prod(nf if to_grid else N))
+    if len(N) != len(nf) or z.shape[1] != 2 * n_in or corr.numel() != sum(N) or corr.dtype != z.dtype:
+        raise ValueError(f"nufft_deconv: N {tuple(N)}, nf {tuple(nf)}, z {tuple(z.shape)}, corr {tuple(corr.shape)} "
+                         "do not match.")
+    out = empty((Q, 2 * n_out), z) if out is None else out
+    check(lib.pxa_nufft_deconv(dtcode(z), len(N), Q, i64_array(N), i64_array(nf), int(modeord), int(bool(to_grid)),
+                               ptr(corr), ptr(z), ptr(out), stream()), "pxa_nufft_deconv")
+    return out
+
+
 _tuning_from_env()

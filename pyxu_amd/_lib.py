@@ -114,6 +114,10 @@ EXPORTS = {
     "pxa_nudft_tiles": (i32, [i32, P_i64, P_i64, P_i64]),
     "pxa_nudft_workspace_bytes": (sz, [i32, i32, i64, i64, i64, i64]),
     "pxa_nudft": (i32, [i32, i32, i64, i64, i64, vp, vp, i32, vp, vp, i64, vp, vp]),
+    "pxa_nufft_grid_tiles": (i32, [i32, i32, P_i64, P_i64, P_i64]),
+    "pxa_nufft_spread": (i32, [i32, i32, i64, i64, P_i64, i32, f64, vp, vp, vp, vp, vp, vp, vp]),
+    "pxa_nufft_interp": (i32, [i32, i32, i64, i64, P_i64, i32, f64, vp, vp, vp, vp, vp, vp]),
+    "pxa_nufft_deconv": (i32, [i32, i32, i64, P_i64, P_i64, i32, i32, vp, vp, vp, vp]),
     "pxa_pds_kernel_ms": (i32, [vp, i32]),
     "pxa_pds_step": (
         i32,

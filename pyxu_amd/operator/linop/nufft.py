@@ -1,9 +1,13 @@
-"""Non-uniform FFT LinOp (reference operator/linop/fft/nufft.py:84-1920), by direct evaluation on pxa_nudft.
+"""Non-uniform FFT LinOp (reference operator/linop/fft/nufft.py:84-1920).
 
-Every transform here is the exact exponential sum the reference computes with ``eps=0`` (``_nudft``,
-nufft.py:2820-2892): O(M N) work on the tiled NUDFT kernel.  The gridding NUFFT (``eps > 0``) is not built; a
-positive ``eps`` is accepted and served by the exact sum, which meets any tolerance.
+Two paths.  The exact exponential sum the reference computes with ``eps=0`` (``_nudft``, nufft.py:2820-2892):
+O(M N) work on the tiled NUDFT kernel (pxa_nudft), for types 1, 2 and 3.  And, for types 1 and 2 with ``eps > 0``,
+the gridding transform the reference delegates to FINUFFT (nufft.py:1367-1400, 1660-1689): spreading with the
+"exponential of semicircle" kernel onto an oversampled grid, an FFT, and a per-mode correction (pxa_nufft_spread /
+pxa_nufft_interp / pxa_nufft_deconv around pxa_fft_ex).  ``method`` chooses; ``"auto"`` grids once M prod(N) reaches
+``GRID_CROSSOVER`` and otherwise serves a positive ``eps`` by the exact sum, which meets any tolerance.
 """
+import math
 import warnings
 
 import numpy as np
@@ -17,9 +21,18 @@ from pyxu_amd.util import as_canonical_shape, is_device_array, to_device, to_NUM
 __all__ = ["NUFFT"]
 
 _EPS_MSG = (
-    "NUFFT: the gridding transform (eps > 0) is not built; eps={eps:g} is served by direct evaluation of the "
-    "exponential sum, which is exact but costs O(M N) = {cost:.3g} complex exponentials per transform."
+    "NUFFT: eps={eps:g} is served by direct evaluation of the exponential sum, which is exact but costs "
+    "O(M N) = {cost:.3g} complex exponentials per transform (the gridding transform serves types 1 and 2 from "
+    "M prod(N) = {floor:.3g} on, or with method='grid')."
 )
+
+# method="auto" grids from this many (point, mode) pairs on.  Measured (scripts/bench_nufft_grid.py):
+# the smallest tested M prod(N) from which the gridded apply and adjoint both beat pxa_nudft in 1, 2 and 3 dimensions
+# at eps = 1e-4 and 1e-6 (in 1 and 2 dimensions they do from 2^20 on; the 3-D spreading at eps = 1e-6 loses or
+# ties up to 2^28).  Never below 2^20 pairs: a direct transform of that size is launch-bound, and the gridded chain is four
+# launches.
+GRID_CROSSOVER = 1 << 30
+_METHODS = ("auto", "grid", "direct")
 
 
 def _as_canonical_coordinate(x):
@@ -64,14 +77,118 @@ def _mesh(N, modeord, dtype):
     return grid
 
 
-def _common(isign, eps, real, enable_warnings, kwargs, cost):
+def _common(isign, eps, real, enable_warnings, kwargs, cost, gridded=False):
     modeord = int(kwargs.get("modeord", 0))
     if modeord not in (0, 1):
         raise ValueError(f"modeord must be 0 or 1, got {modeord}.")
     eps, enable_warnings = float(eps), bool(enable_warnings)
-    if eps > 0 and enable_warnings:
-        warnings.warn(_EPS_MSG.format(eps=eps, cost=float(cost)), UserWarning, stacklevel=3)
+    if eps > 0 and enable_warnings and not gridded:
+        msg = _EPS_MSG.format(eps=eps, cost=float(cost), floor=float(GRID_CROSSOVER))
+        warnings.warn(msg, UserWarning, stacklevel=3)
     return int(np.sign(isign)), bool(real), enable_warnings, modeord
+
+
+def _method(kwargs):
+    method = kwargs.get("method", "auto")
+    if method not in _METHODS:
+        raise ValueError(f"method must be one of {_METHODS}, got {method!r}.")
+    return method
+
+
+def _use_grid(method, eps, pairs):
+    """Whether a type-1 / type-2 transform of `pairs` = M prod(N) runs on the gridding path."""
+    if method == "grid":
+        if not float(eps) > 0:
+            raise ValueError("NUFFT: method='grid' needs eps > 0 (eps = 0 is the exact sum, method='direct').")
+        return True
+    return method == "auto" and float(eps) > 0 and pairs >= GRID_CROSSOVER
+
+
+# ------------------------------------------------------------------ gridding: parameters and plan (host, float64)
+def _grid_sigma(upsampfac):
+    """Upsampling factor: 2 unless the caller asks for 1.25 (None / 0: the default)."""
+    if upsampfac is None or float(upsampfac) in (0.0, 2.0):
+        return 2.0
+    if float(upsampfac) == 1.25:
+        return 1.25
+    raise ValueError(f"upsampfac must be 2 or 1.25, got {upsampfac!r}.")
+
+
+def _grid_kernel(eps, sigma):
+    """(w, beta): support in fine-grid cells and shape of phi(z) = exp(beta (sqrt(1 - z^2) - 1))."""
+    eps = float(eps)
+    guard = 1e-9  # eps = 10^-k gives w = k + 1, whatever the last bit of the logarithm
+    if sigma == 2.0:
+        w = math.ceil(-math.log10(eps) + 1 - guard)
+    else:
+        w = math.ceil(-math.log(eps) / (math.pi * math.sqrt(1 - 1 / sigma)) - guard)
+    w = min(max(w, 2), 16)
+    if sigma == 2.0:
+        beta = {2: 2.20, 3: 2.26, 4: 2.38}.get(w, 2.30) * w
+    else:
+        beta = 0.97 * math.pi * (1 - 0.5 / sigma) * w
+    return w, beta
+
+
+def _smooth_even(n):
+    """Smallest even length >= n whose prime factors are in {2, 3, 5, 7} (the lengths the Stockham FFT handles)."""
+    n = max(int(n), 2)
+    n += n % 2
+    while True:
+        m = n
+        for p in (2, 3, 5, 7):
+            while m % p == 0:
+                m //= p
+        if m == 1:
+            return n
+        n += 2
+
+
+def _grid_size(N, sigma, w):
+    return tuple(_smooth_even(max(math.floor(sigma * n), 2 * w)) for n in N)
+
+
+_GL_NODES = 128
+
+
+def _grid_correction(n, nf, w, beta, nodes=_GL_NODES):
+    """1 / psi_hat(k) for the n modes k = -(n // 2) .. (n - 1) // 2 of an axis of nf cells, with
+    psi_hat(k) = (w / 2) int_{-1}^{1} phi(z) cos(k (2 pi / nf) (w / 2) z) dz.  With z = sin(t) the integrand is
+    entire in t (no square-root end points), and Gauss-Legendre on [-pi/2, pi/2] converges geometrically."""
+    t, wt = np.polynomial.legendre.leggauss(nodes)
+    t, wt = 0.5 * np.pi * t, 0.5 * np.pi * wt
+    k = np.arange(-(n // 2), (n - 1) // 2 + 1, dtype=np.float64)
+    alpha = k * (np.pi * w / nf)
+    f = np.exp(beta * (np.cos(t) - 1.0)) * np.cos(t) * wt
+    psi = 0.5 * w * (np.cos(alpha[:, None] * np.sin(t)[None, :]) @ f)
+    return 1.0 / psi
+
+
+def _grid_plan(x, nf, w, bin_shape, dtype):
+    """Plan of the M points x (M, D) on the fine grid nf: per point and axis the first touched cell
+    l0 = ceil(xi - w/2) (int32) and the offset xi - l0 in [w/2 - 1, w/2] (`dtype`), xi = (x mod 2 pi) nf / 2 pi,
+    both in the order of a stable sort by bin (`perm`: sorted position -> point; `bin_start`: nbins + 1 offsets).
+    A bin is a tile of `bin_shape` cells, its id row-major, and a point belongs to the bin of floor(xi)."""
+    x = np.asarray(x, dtype=np.float64)
+    nf_a, e = np.asarray(nf, dtype=np.int64), np.asarray(bin_shape, dtype=np.int64)
+    xi = np.mod(x, 2 * np.pi) * (nf_a / (2 * np.pi))
+    xi[(xi >= nf_a) | (xi < 0)] = 0.0  # the fold can round up to the period itself
+    l0 = np.ceil(xi - 0.5 * w)
+    off = xi - l0
+    cell = np.minimum(np.floor(xi).astype(np.int64), nf_a - 1)
+    nb = (nf_a + e - 1) // e
+    bins = np.zeros(x.shape[0], dtype=np.int64)
+    for d in range(x.shape[1]):
+        bins = bins * nb[d] + cell[:, d] // e[d]
+    perm = np.argsort(bins, kind="stable").astype(np.int64)
+    counts = np.bincount(bins, minlength=int(np.prod(nb)))
+    bin_start = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    return dict(
+        l0=np.ascontiguousarray(l0[perm].astype(np.int32)),
+        off=np.ascontiguousarray(off[perm].astype(dtype)),
+        perm=perm,
+        bin_start=bin_start,
+    )
 
 
 def _NUFFT12_args(x, N):
@@ -90,8 +207,16 @@ class NUFFT(pxa.LinOp):
     (non-uniform -> non-uniform) in 1, 2 or 3 dimensions (nufft.py:84-737), evaluated exactly.
 
     Complex arrays are real views ``(..., 2 K)`` of interleaved (re, im) pairs; leading dimensions are a stack.
-    ``eps > 0`` is served by the exact sum (with a ``UserWarning`` naming its O(M N) cost); ``n_trans``,
-    ``upsampfac``, ``plan_fw`` / ``plan_bw`` and the other FINUFFT options are accepted and have no effect.
+
+    ``type1`` / ``type2`` take ``method="auto" | "grid" | "direct"``.  ``"direct"`` is the exact sum (O(M N)).
+    ``"grid"`` (needs ``eps > 0``) is the gridding transform to relative accuracy ``eps``: kernel width and shape
+    from ``eps`` and ``upsampfac`` (2, the default, or 1.25; anything else is a ``ValueError``), a plan built on the
+    host at construction.  ``"auto"`` grids when ``eps > 0`` and M prod(N) >= ``GRID_CROSSOVER`` and otherwise takes
+    the exact sum, with a ``UserWarning`` naming its cost when ``eps > 0``.  ``apply`` and ``adjoint`` of a gridded
+    operator are exact adjoints of each other (to rounding, not merely to ``eps``); its ``asarray`` /
+    ``ascomplexarray`` are the exact transform's matrix, which the operator matches to ``eps``.  ``type3`` is always
+    the exact sum.  ``n_trans``, ``plan_fw`` / ``plan_bw`` and the other FINUFFT options are accepted and have no
+    effect.
     """
 
     def __init__(self, shape):
@@ -102,8 +227,12 @@ class NUFFT(pxa.LinOp):
     def type1(x, N, isign=1, eps=1e-4, real=False, plan_fw=True, plan_bw=True, enable_warnings=True, **kwargs):
         r"""u_n = \sum_j w_j exp(i isign <n, x_j>): (..., [2] M) -> (..., 2 prod N) (nufft.py:337-434)."""
         x, N = _NUFFT12_args(x, N)
-        isign, real, ew, modeord = _common(isign, eps, real, enable_warnings, kwargs, x.shape[0] * np.prod(N))
+        pairs = x.shape[0] * int(np.prod(N))
+        sigma, gridded = _grid_sigma(kwargs.get("upsampfac")), _use_grid(_method(kwargs), eps, pairs)
+        isign, real, ew, modeord = _common(isign, eps, real, enable_warnings, kwargs, pairs, gridded)
         grid = _mesh(N, modeord, x.dtype).reshape(-1, x.shape[1])
+        if gridded:
+            return _NUFFTGrid(1, x, grid, isign, real, ew, N, modeord, eps, sigma)
         return _NUDFT(x, grid, isign, real, ew, mode=N, modeord=modeord)
 
     @staticmethod
@@ -111,8 +240,12 @@ class NUFFT(pxa.LinOp):
     def type2(x, N, isign=1, eps=1e-4, real=False, plan_fw=True, plan_bw=True, enable_warnings=True, **kwargs):
         r"""w_j = \sum_n u_n exp(i isign <n, x_j>): (..., [2] prod N) -> (..., 2 M) (nufft.py:438-546)."""
         x, N = _NUFFT12_args(x, N)
-        isign, real, ew, modeord = _common(isign, eps, real, enable_warnings, kwargs, x.shape[0] * np.prod(N))
+        pairs = x.shape[0] * int(np.prod(N))
+        sigma, gridded = _grid_sigma(kwargs.get("upsampfac")), _use_grid(_method(kwargs), eps, pairs)
+        isign, real, ew, modeord = _common(isign, eps, real, enable_warnings, kwargs, pairs, gridded)
         grid = _mesh(N, modeord, x.dtype).reshape(-1, x.shape[1])
+        if gridded:
+            return _NUFFTGrid(2, x, grid, isign, real, ew, N, modeord, eps, sigma)
         return _NUDFT(grid, x, isign, real, ew, mode=N, modeord=modeord)
 
     @staticmethod
@@ -122,6 +255,8 @@ class NUFFT(pxa.LinOp):
         r"""v_k = \sum_j w_j exp(i isign <z_k, x_j>): (..., [2] M) -> (..., 2 N) (nufft.py:550-737)."""
         if bool(chunked):
             raise NotImplementedError("NUFFT.type3(chunked=True) is not available: the transform is evaluated directly.")
+        if _method(kwargs) == "grid":
+            raise NotImplementedError("NUFFT.type3(method='grid'): the type-3 gridding transform is not built.")
         x, z = _as_canonical_coordinate(x), _as_canonical_coordinate(z)
         assert x.shape[-1] == z.shape[-1], "x vs. z: dimensionality mis-match."
         kwargs.pop("modeord", None)
@@ -199,8 +334,68 @@ class _NUDFT(NUFFT):
     def mesh(self, xp=None, dtype=None, scale="unit", upsampled=False):
         """(N1, ..., Nd, d) mode grid of a type-1 / type-2 transform (nufft.py:1612-1642)."""
         if self._mode is None:
-            raise NotImplementedError("NUFFT.mesh(): the type-3 grids belong to the gridding transform (not built).")
+            raise NotImplementedError("NUFFT.mesh(): the type-3 grids belong to its gridding transform (not built).")
         if scale != "unit" or upsampled:
-            raise NotImplementedError("NUFFT.mesh(): only scale='unit', upsampled=False (direct evaluation).")
+            raise NotImplementedError("NUFFT.mesh(): only scale='unit', upsampled=False.")
         dtype = pxrt.getPrecision().value if dtype is None else dtype
         return _mesh(self._mode, self._modeord, dtype)
+
+
+class _NUFFTGrid(_NUDFT):
+    r"""Type-1 / type-2 transform of accuracy ``eps`` on the oversampled grid.  With S the spreading matrix of the
+    plan, F the unnormalised DFT of sign ``isign`` on the fine grid, T the restriction to the N central modes and C
+    the diagonal correction, type 1 is C T F S and type 2 is S^T F T^T C; each is the adjoint of the other with the
+    opposite sign, so ``apply`` and ``adjoint`` share one plan and both kernels.  Shapes, ``mesh``, ``lipschitz``,
+    ``asarray`` / ``ascomplexarray`` (the exact transform's matrix) come from the exact operator."""
+
+    def __init__(self, typ, x, grid, isign, real, enable_warnings, N, modeord, eps, sigma):
+        src, tgt = (x, grid) if typ == 1 else (grid, x)
+        super().__init__(src, tgt, isign, real, enable_warnings, mode=N, modeord=modeord)
+        self._typ, self._eps, self._sigma = int(typ), float(eps), float(sigma)
+        self._w, self._beta = _grid_kernel(eps, sigma)
+        self._nf = _grid_size(N, sigma, self._w)
+        code = 0 if x.dtype == np.float32 else 1
+        self._bin_shape = _dev.nufft_grid_tiles(code, self._D)[0]
+        self._plan = _grid_plan(x, self._nf, self._w, self._bin_shape, x.dtype)
+        self._plan["corr"] = np.concatenate(
+            [_grid_correction(n, nf, self._w, self._beta) for n, nf in zip(N, self._nf)]
+        ).astype(x.dtype)
+        self._plan_dev = None  # uploaded at first use
+
+    def _device_plan(self):
+        if self._plan_dev is None:
+            p = self._plan
+            self._plan_dev = tuple(to_device(p[k]) for k in ("l0", "off", "perm", "bin_start", "corr"))
+        return self._plan_dev
+
+    def _type1(self, c, isign):
+        """c (Q, 2 M) -> modes (Q, 2 prod N): spread, FFT, extract and correct."""
+        *plan, corr = self._device_plan()
+        g = _dev.nufft_spread(self._nf, self._w, self._beta, plan, c)
+        _dev.fft(g, self._nf, tuple(range(self._D)), g.shape[0], isign > 0, out=g)
+        return _dev.nufft_deconv(self._mode, self._nf, self._modeord, False, corr, g)
+
+    def _type2(self, u, isign):
+        """modes u (Q, 2 prod N) -> (Q, 2 M): correct and zero-embed, FFT, interpolate."""
+        *plan, corr = self._device_plan()
+        g = _dev.nufft_deconv(self._mode, self._nf, self._modeord, True, corr, u)
+        _dev.fft(g, self._nf, tuple(range(self._D)), g.shape[0], isign > 0, out=g)
+        return _dev.nufft_interp(self._nf, self._w, self._beta, plan, g)
+
+    @pxrt.enforce_precision(i="arr")
+    def apply(self, arr):
+        arr = self._warn_cast(_dev.require(arr, "arr"))
+        w, sh = self._stacked(arr, self.dim)
+        if self._real:
+            w = _dev.real_to_complex(w)
+        out = (self._type1 if self._typ == 1 else self._type2)(w, self._isign)
+        return out.reshape(*sh, self.codim)
+
+    @pxrt.enforce_precision(i="arr")
+    def adjoint(self, arr):
+        arr = self._warn_cast(_dev.require(arr, "arr"))
+        w, sh = self._stacked(arr, self.codim)
+        out = (self._type2 if self._typ == 1 else self._type1)(w, -self._isign)
+        if self._real:
+            out = _dev.complex_real_part(out)
+        return out.reshape(*sh, self.dim)
