@@ -643,6 +643,15 @@ int pxa_nudft(int dtype, int D, int64_t Q, int64_t M, int64_t N, const void* src
  *   1: FFT order.  to_grid = 1: out (Q, nf..) = in (Q, n..) scaled, mode k in cell k mod nf, zero elsewhere;
  *   to_grid = 0: out (Q, n..) = the modes' cells of in (Q, nf..), scaled.  No fftshift copy exists.
  * None of them allocates or synchronises.  Q = 0 does nothing; M = 0 spreads zeros.
+ *
+ * Type 3 (NUFFT.type3 with eps > 0) is spread_fac of the rescaled sources onto an outer grid nf1, deconv with
+ * n = nf1, nf = nf2, modeord 1, to_grid 1 (the spread grid is the inner type 2's modes in FFT order), the FFT on
+ * nf2, and interp_fac at the rescaled targets; its adjoint is the transposed chain.
+ * pxa_nufft_spread_fac / pxa_nufft_interp_fac: the same kernels with one complex factor per point, fac (M)
+ *   interleaved complex in sorted order (entry s belongs to point perm[s]), conjugated when conj_fac = 1
+ *   (conj_fac must be 0 or 1).  spread_fac spreads c[q, perm[s]] fac[s]; interp_fac stores the finished sum times
+ *   fac[s].  One complex product per (point, row) in the working precision; the order of the sums, and so the
+ *   bits for a given input, are those of the plain kernels.
  * ------------------------------------------------------------------------------------------- */
 int pxa_nufft_grid_tiles(int dtype, int D, int64_t* bin_shape /* [3] */, int64_t* q_chunk, int64_t* batch);
 int pxa_nufft_spread(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
@@ -653,6 +662,12 @@ int pxa_nufft_interp(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, 
                      void* stream);
 int pxa_nufft_deconv(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* nf, int modeord, int to_grid,
                      const void* corr, const void* in, void* out, void* stream);
+int pxa_nufft_spread_fac(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                         const int32_t* l0, const void* off, const int64_t* perm, const int64_t* bin_start,
+                         const void* c, void* grid, const void* fac, int conj_fac, void* stream);
+int pxa_nufft_interp_fac(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                         const int32_t* l0, const void* off, const int64_t* perm, const void* grid, void* out,
+                         const void* fac, int conj_fac, void* stream);
 
 /* Measurement hook: with pxa_tuning(PXA_TUNE_PDS_EVENTS, 1), pxa_pds_step / pxa_pds_step_la record HIP
  * events around their kernels (at most 64 steps).  This call waits for the last of them and writes into

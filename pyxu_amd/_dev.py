@@ -1450,8 +1450,17 @@ def _nufft_plan_check(plan, name):
     return M, D
 
 
-def nufft_spread(nf, w, beta, plan, c, out=None):
-    """grid (Q, 2 prod nf) = spread of c (Q, 2 M) with the plan (l0, off, perm, bin_start) (pxa_nufft_spread)."""
+def _nufft_fac_check(fac, M, like, name):
+    fac = require(fac, "fac")
+    if fac.numel() != 2 * M or fac.dtype != like.dtype:
+        raise ValueError(f"{name}: fac {tuple(fac.shape)} {fac.dtype} does not match {M} points of {like.dtype}.")
+    return fac
+
+
+def nufft_spread(nf, w, beta, plan, c, out=None, fac=None, conj=False):
+    """grid (Q, 2 prod nf) = spread of c (Q, 2 M) with the plan (l0, off, perm, bin_start) (pxa_nufft_spread).  With
+    `fac` (2 M interleaved complex, in the plan's sorted order) every point's weights are multiplied by its factor,
+    conjugated with `conj` (pxa_nufft_spread_fac)."""
     c = require(c, "c")
     M, D = _nufft_plan_check(plan, "nufft_spread")
     l0, off, perm, bin_start = plan
@@ -1462,13 +1471,21 @@ def nufft_spread(nf, w, beta, plan, c, out=None):
     if bin_start.numel() != nbins + 1:
         raise ValueError(f"nufft_spread: bin_start has {bin_start.numel()} entries, the grid {nbins} bins.")
     out = empty((Q, 2 * int(np.prod(nf))), c) if out is None else out
+    if fac is not None:
+        fac = _nufft_fac_check(fac, M, c, "nufft_spread")
+        check(lib.pxa_nufft_spread_fac(dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
+                                       ptr(perm), ptr(bin_start), ptr(c), ptr(out), ptr(fac), int(bool(conj)),
+                                       stream()), "pxa_nufft_spread_fac")
+        return out
     check(lib.pxa_nufft_spread(dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off), ptr(perm),
                                ptr(bin_start), ptr(c), ptr(out), stream()), "pxa_nufft_spread")
     return out
 
 
-def nufft_interp(nf, w, beta, plan, grid, out=None):
-    """out (Q, 2 M) = interpolation of grid (Q, 2 prod nf) at the plan's points (pxa_nufft_interp)."""
+def nufft_interp(nf, w, beta, plan, grid, out=None, fac=None, conj=False):
+    """out (Q, 2 M) = interpolation of grid (Q, 2 prod nf) at the plan's points (pxa_nufft_interp).  With `fac`
+    (2 M interleaved complex, in the plan's sorted order) every point's result is multiplied by its factor,
+    conjugated with `conj` (pxa_nufft_interp_fac)."""
     grid = require(grid, "grid")
     M, D = _nufft_plan_check(plan, "nufft_interp")
     l0, off, perm, _ = plan
@@ -1476,6 +1493,12 @@ def nufft_interp(nf, w, beta, plan, grid, out=None):
     if len(nf) != D or grid.shape[1] != 2 * int(np.prod(nf)) or off.dtype != grid.dtype:
         raise ValueError(f"nufft_interp: nf {tuple(nf)}, off {tuple(off.shape)}, grid {tuple(grid.shape)} do not match.")
     out = empty((Q, 2 * M), grid) if out is None else out
+    if fac is not None:
+        fac = _nufft_fac_check(fac, M, grid, "nufft_interp")
+        check(lib.pxa_nufft_interp_fac(dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
+                                       ptr(perm), ptr(grid), ptr(out), ptr(fac), int(bool(conj)), stream()),
+              "pxa_nufft_interp_fac")
+        return out
     check(lib.pxa_nufft_interp(dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
                                ptr(perm), ptr(grid), ptr(out), stream()), "pxa_nufft_interp")
     return out

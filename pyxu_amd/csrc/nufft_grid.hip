@@ -1,5 +1,7 @@
-// pyxu_amd — gridding NUFFT, types 1 and 2 (what the reference delegates to FINUFFT for eps > 0,
+// pyxu_amd — gridding NUFFT (what the reference delegates to FINUFFT for eps > 0,
 // operator/linop/fft/nufft.py:1367-1400, 1660-1689): the three kernels around the FFT on the oversampled grid.
+// Types 1 and 2 use them as they are; type 3 (spread the rescaled sources, then a type 2 of that grid to the rescaled
+// targets) uses spread and interp with one complex factor per point (template parameter FAC, pxa_nufft_*_fac).
 //
 //   spread : grid[q, l]  = sum_j c[q, j] prod_d phi(2 (l_d - xi_jd) / w)     points -> fine grid (periodic)
 //   interp : c[q, j]     = sum_l grid[q, l] prod_d phi(2 (l_d - xi_jd) / w)  fine grid -> points (its transpose)
@@ -81,6 +83,17 @@ __device__ inline float fma_g<float>(float a, float b, float c) {
   return __builtin_fmaf(a, b, c);
 }
 
+// (a + i b) (c + i d), each part one product and one fused multiply-add, spelled out so that every instantiation
+// rounds alike
+template <typename T>
+__device__ inline T cmul_re(T a, T b, T c, T d) {
+  return fma_g<T>(a, c, -(b * d));
+}
+template <typename T>
+__device__ inline T cmul_im(T a, T b, T c, T d) {
+  return fma_g<T>(a, d, b * c);
+}
+
 // phi(2 x / w), x = l - xi
 template <typename T>
 __device__ inline T es_phi(T x, T two_over_w, T beta) {
@@ -97,12 +110,14 @@ __device__ inline int fold_cell(int32_t l0, int nf) {
   return v;
 }
 
-template <typename T, int D, int QC>
+// FAC: every point's weights are multiplied by its complex factor fac[s] (sorted order; conjugated if conj_fac)
+template <typename T, int D, int QC, bool FAC>
 __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64_t M, int w, T two_over_w, T beta,
                                                         const int32_t* __restrict__ l0, const T* __restrict__ off,
                                                         const int64_t* __restrict__ perm,
                                                         const int64_t* __restrict__ bin_start,
-                                                        const T* __restrict__ c, T* __restrict__ grid) {
+                                                        const T* __restrict__ c, T* __restrict__ grid,
+                                                        const T* __restrict__ fac, int conj_fac) {
   using Tl = Tile<D>;
   constexpr int E[3] = {Tl::e0, Tl::e1, Tl::e2};
   constexpr int CPT = Tl::e0 * Tl::e1 * Tl::e2 / kBlock;
@@ -187,8 +202,14 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64
         int cl[D];
         T co[D];
         int64_t cp = 0;
-        auto fetch = [&](int64_t s, int (&fl)[D], T (&fo)[D], int64_t& fp) {
+        T cf[2] = {(T)1, (T)0};
+        auto fetch = [&](int64_t s, int (&fl)[D], T (&fo)[D], int64_t& fp, T (&ff)[2]) {
           const bool in = s < hi;
+          if constexpr (FAC) {
+            ff[0] = in ? fac[s * 2] : (T)1;
+            ff[1] = in ? fac[s * 2 + 1] : (T)0;
+            if (conj_fac) ff[1] = -ff[1];
+          }
 #pragma unroll
           for (int d = 0; d < D; ++d) {
             fl[d] = in ? fold_cell(l0[s * D + d], nf[d]) : 0;
@@ -196,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64
           }
           fp = in ? perm[s] : 0;
         };
-        fetch(lo + t, cl, co, cp);
+        fetch(lo + t, cl, co, cp, cf);
         for (int64_t s0 = lo; s0 < hi; s0 += kBatch) {
           // which candidates' footprints meet the tile
           bool meets = s0 + t < hi;
@@ -211,11 +232,17 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64
             const bool ok = meets && q0 + q < Q && (uint64_t)cp < (uint64_t)M;
             cw[q][0] = ok ? c[((q0 + q) * M + cp) * 2] : (T)0;
             cw[q][1] = ok ? c[((q0 + q) * M + cp) * 2 + 1] : (T)0;
+            if constexpr (FAC) {
+              const T re = cmul_re<T>(cw[q][0], cw[q][1], cf[0], cf[1]);
+              cw[q][1] = cmul_im<T>(cw[q][0], cw[q][1], cf[0], cf[1]);
+              cw[q][0] = re;
+            }
           }
           int ncl[D];
           T nco[D];
           int64_t ncp;
-          fetch(s0 + kBatch + t, ncl, nco, ncp);
+          T ncf[2] = {(T)1, (T)0};
+          fetch(s0 + kBatch + t, ncl, nco, ncp, ncf);
 
           const unsigned long long bal = __ballot(meets);
           if (lane == 0) s_wcnt[wave] = __popcll(bal);
@@ -283,6 +310,10 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64
             co[d] = nco[d];
           }
           cp = ncp;
+          if constexpr (FAC) {
+            cf[0] = ncf[0];
+            cf[1] = ncf[1];
+          }
         }
       }
 
@@ -301,12 +332,14 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Geom g, int64_t Q, int64
   }
 }
 
-template <typename T, int D, int QC>
+// FAC: every point's finished sum is multiplied by its complex factor fac[s] (sorted order; conjugated if conj_fac)
+template <typename T, int D, int QC, bool FAC>
 __global__ __launch_bounds__(kInterpBlock) void interp_kernel(Geom g, int64_t Q, int64_t M, int w, T two_over_w,
                                                               T beta, const int32_t* __restrict__ l0,
                                                               const T* __restrict__ off,
                                                               const int64_t* __restrict__ perm,
-                                                              const T* __restrict__ grid, T* __restrict__ out) {
+                                                              const T* __restrict__ grid, T* __restrict__ out,
+                                                              const T* __restrict__ fac, int conj_fac) {
   extern __shared__ __attribute__((aligned(16))) unsigned char s_raw[];
   T* s_ker = (T*)s_raw;  // [d][i][thread]
   const int t = threadIdx.x;
@@ -314,6 +347,11 @@ __global__ __launch_bounds__(kInterpBlock) void interp_kernel(Geom g, int64_t Q,
   if (s >= M) return;
   const int64_t pm = perm[s];
   if ((uint64_t)pm >= (uint64_t)M) return;
+  T f[2] = {(T)1, (T)0};
+  if constexpr (FAC) {
+    f[0] = fac[s * 2];
+    f[1] = conj_fac ? -fac[s * 2 + 1] : fac[s * 2 + 1];
+  }
   int c0[3] = {0, 0, 0};
 #pragma unroll
   for (int d = 0; d < D; ++d) {
@@ -355,8 +393,13 @@ __global__ __launch_bounds__(kInterpBlock) void interp_kernel(Geom g, int64_t Q,
   for (int q = 0; q < QC; ++q) {
     if (q0 + q >= Q) break;
     T* o = out + ((q0 + q) * M + pm) * 2;
-    o[0] = acc[q][0];
-    o[1] = acc[q][1];
+    if constexpr (FAC) {
+      o[0] = cmul_re<T>(acc[q][0], acc[q][1], f[0], f[1]);
+      o[1] = cmul_im<T>(acc[q][0], acc[q][1], f[0], f[1]);
+    } else {
+      o[0] = acc[q][0];
+      o[1] = acc[q][1];
+    }
   }
 }
 
@@ -452,42 +495,87 @@ bool make_geom(int D, int64_t Q, int64_t M, const int64_t* nf, const int64_t* n,
 
 int q_chunk_for(int64_t Q) { return Q >= 3 ? kGridQChunk : (int)Q; }  // 3 rows run as a padded chunk of 4
 
-template <typename T, int D>
+template <typename T, int D, bool FAC>
 int spread_launch(const Geom& g, int64_t nbins, int64_t Q, int64_t M, int w, double beta, const int32_t* l0,
                   const void* off, const int64_t* perm, const int64_t* bin_start, const void* c, void* grid,
-                  hipStream_t st) {
+                  const void* fac, int conj_fac, hipStream_t st) {
   const int qc = q_chunk_for(Q);
   const dim3 gr((unsigned)nbins, (unsigned)((Q + qc - 1) / qc));
   const T tw = (T)(2.0 / w), b = (T)beta;
   if (qc == 1)
-    hipLaunchKernelGGL((spread_kernel<T, D, 1>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0, (const T*)off, perm,
-                       bin_start, (const T*)c, (T*)grid);
+    hipLaunchKernelGGL((spread_kernel<T, D, 1, FAC>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0, (const T*)off, perm,
+                       bin_start, (const T*)c, (T*)grid, (const T*)fac, conj_fac);
   else if (qc == 2)
-    hipLaunchKernelGGL((spread_kernel<T, D, 2>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0, (const T*)off, perm,
-                       bin_start, (const T*)c, (T*)grid);
+    hipLaunchKernelGGL((spread_kernel<T, D, 2, FAC>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0, (const T*)off, perm,
+                       bin_start, (const T*)c, (T*)grid, (const T*)fac, conj_fac);
   else
-    hipLaunchKernelGGL((spread_kernel<T, D, kGridQChunk>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0,
-                       (const T*)off, perm, bin_start, (const T*)c, (T*)grid);
+    hipLaunchKernelGGL((spread_kernel<T, D, kGridQChunk, FAC>), gr, dim3(kBlock), 0, st, g, Q, M, w, tw, b, l0,
+                       (const T*)off, perm, bin_start, (const T*)c, (T*)grid, (const T*)fac, conj_fac);
   return last_launch_status();
 }
 
-template <typename T, int D>
+template <typename T, int D, bool FAC>
 int interp_launch(const Geom& g, int64_t Q, int64_t M, int w, double beta, const int32_t* l0, const void* off,
-                  const int64_t* perm, const void* grid, void* out, hipStream_t st) {
+                  const int64_t* perm, const void* grid, void* out, const void* fac, int conj_fac, hipStream_t st) {
   const int qc = q_chunk_for(Q);
   const dim3 gr((unsigned)((M + kInterpBlock - 1) / kInterpBlock), (unsigned)((Q + qc - 1) / qc));
   const size_t lds = (size_t)D * w * kInterpBlock * sizeof(T);  // <= 48 KiB
   const T tw = (T)(2.0 / w), b = (T)beta;
   if (qc == 1)
-    hipLaunchKernelGGL((interp_kernel<T, D, 1>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
-                       (const T*)off, perm, (const T*)grid, (T*)out);
+    hipLaunchKernelGGL((interp_kernel<T, D, 1, FAC>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
+                       (const T*)off, perm, (const T*)grid, (T*)out, (const T*)fac, conj_fac);
   else if (qc == 2)
-    hipLaunchKernelGGL((interp_kernel<T, D, 2>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
-                       (const T*)off, perm, (const T*)grid, (T*)out);
+    hipLaunchKernelGGL((interp_kernel<T, D, 2, FAC>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
+                       (const T*)off, perm, (const T*)grid, (T*)out, (const T*)fac, conj_fac);
   else
-    hipLaunchKernelGGL((interp_kernel<T, D, kGridQChunk>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
-                       (const T*)off, perm, (const T*)grid, (T*)out);
+    hipLaunchKernelGGL((interp_kernel<T, D, kGridQChunk, FAC>), gr, dim3(kInterpBlock), lds, st, g, Q, M, w, tw, b, l0,
+                       (const T*)off, perm, (const T*)grid, (T*)out, (const T*)fac, conj_fac);
   return last_launch_status();
+}
+
+template <bool FAC>
+int spread_entry(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta, const int32_t* l0,
+                 const void* off, const int64_t* perm, const int64_t* bin_start, const void* c, void* grid,
+                 const void* fac, int conj_fac, void* stream) {
+  if (dtype != PXA_F32 && dtype != PXA_F64) return PXA_ERR_DTYPE;
+  if (D < 1 || D > 3) return PXA_ERR_UNSUPPORTED;
+  Geom g;
+  int64_t nbins = 0;
+  PXA_CHECK_ARG(w >= 2 && beta > 0 && make_geom(D, Q, M, nf, nullptr, w, &g, &nbins));
+  PXA_CHECK_ARG(!FAC || conj_fac == 0 || conj_fac == 1);
+  if (Q == 0) return PXA_OK;
+  if ((Q + kGridQChunk - 1) / kGridQChunk > 65535) return PXA_ERR_UNSUPPORTED;
+  PXA_CHECK_ARG(grid && bin_start && (M == 0 || (l0 && off && perm && c && (!FAC || fac))));
+  hipStream_t st = as_stream(stream);
+  PXA_DISPATCH(dtype, T, {
+    if (D == 1)
+      return spread_launch<T, 1, FAC>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, fac, conj_fac, st);
+    if (D == 2)
+      return spread_launch<T, 2, FAC>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, fac, conj_fac, st);
+    return spread_launch<T, 3, FAC>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, fac, conj_fac, st);
+  });
+}
+
+template <bool FAC>
+int interp_entry(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta, const int32_t* l0,
+                 const void* off, const int64_t* perm, const void* grid, void* out, const void* fac, int conj_fac,
+                 void* stream) {
+  if (dtype != PXA_F32 && dtype != PXA_F64) return PXA_ERR_DTYPE;
+  if (D < 1 || D > 3) return PXA_ERR_UNSUPPORTED;
+  Geom g;
+  int64_t nbins = 0;
+  PXA_CHECK_ARG(w >= 2 && beta > 0 && make_geom(D, Q, M, nf, nullptr, w, &g, &nbins));
+  PXA_CHECK_ARG(!FAC || conj_fac == 0 || conj_fac == 1);
+  if (Q == 0 || M == 0) return PXA_OK;
+  if ((Q + kGridQChunk - 1) / kGridQChunk > 65535 || (M + kInterpBlock - 1) / kInterpBlock > 0x7fffffff)
+    return PXA_ERR_UNSUPPORTED;
+  PXA_CHECK_ARG(grid && out && l0 && off && perm && (!FAC || fac));
+  hipStream_t st = as_stream(stream);
+  PXA_DISPATCH(dtype, T, {
+    if (D == 1) return interp_launch<T, 1, FAC>(g, Q, M, w, beta, l0, off, perm, grid, out, fac, conj_fac, st);
+    if (D == 2) return interp_launch<T, 2, FAC>(g, Q, M, w, beta, l0, off, perm, grid, out, fac, conj_fac, st);
+    return interp_launch<T, 3, FAC>(g, Q, M, w, beta, l0, off, perm, grid, out, fac, conj_fac, st);
+  });
 }
 
 }  // namespace
@@ -510,40 +598,25 @@ int pxa_nufft_grid_tiles(int dtype, int D, int64_t* bin_shape, int64_t* q_chunk,
 int pxa_nufft_spread(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
                      const int32_t* l0, const void* off, const int64_t* perm, const int64_t* bin_start,
                      const void* c, void* grid, void* stream) {
-  if (dtype != PXA_F32 && dtype != PXA_F64) return PXA_ERR_DTYPE;
-  if (D < 1 || D > 3) return PXA_ERR_UNSUPPORTED;
-  Geom g;
-  int64_t nbins = 0;
-  PXA_CHECK_ARG(w >= 2 && beta > 0 && make_geom(D, Q, M, nf, nullptr, w, &g, &nbins));
-  if (Q == 0) return PXA_OK;
-  if ((Q + kGridQChunk - 1) / kGridQChunk > 65535) return PXA_ERR_UNSUPPORTED;
-  PXA_CHECK_ARG(grid && bin_start && (M == 0 || (l0 && off && perm && c)));
-  hipStream_t st = as_stream(stream);
-  PXA_DISPATCH(dtype, T, {
-    if (D == 1) return spread_launch<T, 1>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, st);
-    if (D == 2) return spread_launch<T, 2>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, st);
-    return spread_launch<T, 3>(g, nbins, Q, M, w, beta, l0, off, perm, bin_start, c, grid, st);
-  });
+  return spread_entry<false>(dtype, D, Q, M, nf, w, beta, l0, off, perm, bin_start, c, grid, nullptr, 0, stream);
+}
+
+int pxa_nufft_spread_fac(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                         const int32_t* l0, const void* off, const int64_t* perm, const int64_t* bin_start,
+                         const void* c, void* grid, const void* fac, int conj_fac, void* stream) {
+  return spread_entry<true>(dtype, D, Q, M, nf, w, beta, l0, off, perm, bin_start, c, grid, fac, conj_fac, stream);
 }
 
 int pxa_nufft_interp(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
                      const int32_t* l0, const void* off, const int64_t* perm, const void* grid, void* out,
                      void* stream) {
-  if (dtype != PXA_F32 && dtype != PXA_F64) return PXA_ERR_DTYPE;
-  if (D < 1 || D > 3) return PXA_ERR_UNSUPPORTED;
-  Geom g;
-  int64_t nbins = 0;
-  PXA_CHECK_ARG(w >= 2 && beta > 0 && make_geom(D, Q, M, nf, nullptr, w, &g, &nbins));
-  if (Q == 0 || M == 0) return PXA_OK;
-  if ((Q + kGridQChunk - 1) / kGridQChunk > 65535 || (M + kInterpBlock - 1) / kInterpBlock > 0x7fffffff)
-    return PXA_ERR_UNSUPPORTED;
-  PXA_CHECK_ARG(grid && out && l0 && off && perm);
-  hipStream_t st = as_stream(stream);
-  PXA_DISPATCH(dtype, T, {
-    if (D == 1) return interp_launch<T, 1>(g, Q, M, w, beta, l0, off, perm, grid, out, st);
-    if (D == 2) return interp_launch<T, 2>(g, Q, M, w, beta, l0, off, perm, grid, out, st);
-    return interp_launch<T, 3>(g, Q, M, w, beta, l0, off, perm, grid, out, st);
-  });
+  return interp_entry<false>(dtype, D, Q, M, nf, w, beta, l0, off, perm, grid, out, nullptr, 0, stream);
+}
+
+int pxa_nufft_interp_fac(int dtype, int D, int64_t Q, int64_t M, const int64_t* nf, int w, double beta,
+                         const int32_t* l0, const void* off, const int64_t* perm, const void* grid, void* out,
+                         const void* fac, int conj_fac, void* stream) {
+  return interp_entry<true>(dtype, D, Q, M, nf, w, beta, l0, off, perm, grid, out, fac, conj_fac, stream);
 }
 
 int pxa_nufft_deconv(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* nf, int modeord, int to_grid,

@@ -1,11 +1,14 @@
 """Non-uniform FFT LinOp (reference operator/linop/fft/nufft.py:84-1920).
 
 Two paths.  The exact exponential sum the reference computes with ``eps=0`` (``_nudft``, nufft.py:2820-2892):
-O(M N) work on the tiled NUDFT kernel (pxa_nudft), for types 1, 2 and 3.  And, for types 1 and 2 with ``eps > 0``,
-the gridding transform the reference delegates to FINUFFT (nufft.py:1367-1400, 1660-1689): spreading with the
-"exponential of semicircle" kernel onto an oversampled grid, an FFT, and a per-mode correction (pxa_nufft_spread /
-pxa_nufft_interp / pxa_nufft_deconv around pxa_fft_ex).  ``method`` chooses; ``"auto"`` grids once M prod(N) reaches
-``GRID_CROSSOVER`` and otherwise serves a positive ``eps`` by the exact sum, which meets any tolerance.
+O(M N) work on the tiled NUDFT kernel (pxa_nudft), for types 1, 2 and 3.  And, with ``eps > 0``, the gridding
+transform the reference delegates to FINUFFT (nufft.py:1367-1400, 1660-1689): spreading with the "exponential of
+semicircle" kernel onto an oversampled grid, an FFT, and a per-mode correction (pxa_nufft_spread /
+pxa_nufft_interp / pxa_nufft_deconv around pxa_fft_ex).  Type 3 rescales sources and targets, spreads the sources
+onto an outer grid and runs a type-2 transform of that grid to the rescaled targets, with a complex factor per
+source and per target (pxa_nufft_spread_fac / pxa_nufft_interp_fac).  ``method`` chooses; ``"auto"`` grids once
+the transform is large enough (``GRID_CROSSOVER``; for type 3 ``GRID_CROSSOVER_T3``, ``T3_PAIRS_PER_CELL`` and
+``GRID_MAX_CELLS``) and otherwise serves a positive ``eps`` by the exact sum, which meets any tolerance.
 """
 import math
 import warnings
@@ -22,8 +25,8 @@ __all__ = ["NUFFT"]
 
 _EPS_MSG = (
     "NUFFT: eps={eps:g} is served by direct evaluation of the exponential sum, which is exact but costs "
-    "O(M N) = {cost:.3g} complex exponentials per transform (the gridding transform serves types 1 and 2 from "
-    "M prod(N) = {floor:.3g} on, or with method='grid')."
+    "O(M N) = {cost:.3g} complex exponentials per transform (the gridding transform takes over from {floor:.3g} "
+    "(point, mode) pairs on, or when forced: method='grid' for types 1 and 2, method='grid3' for type 3)."
 )
 
 # method="auto" grids from this many (point, mode) pairs on.  Measured (scripts/bench_nufft_grid.py):
@@ -32,7 +35,21 @@ _EPS_MSG = (
 # ties up to 2^28).  Never below 2^20 pairs: a direct transform of that size is launch-bound, and the gridded chain is four
 # launches.
 GRID_CROSSOVER = 1 << 30
-_METHODS = ("auto", "grid", "direct")
+# Type 3, method="auto": grids iff eps > 0, prod(nf2) <= GRID_MAX_CELLS and
+# M N >= max(GRID_CROSSOVER_T3, T3_PAIRS_PER_CELL prod(nf2)), nf2 the inner fine grid.  The grid of a type-3 transform
+# follows the space-bandwidth product prod(X_d S_d) of the point clouds, not a mode count the caller chose, so the
+# second term keeps a sparse transform on a huge grid with the exact sum.  Measured (scripts/bench_nufft_type3.py,
+# DESIGN.md §8j), by the rule of GRID_CROSSOVER.  GRID_CROSSOVER_T3: the smallest tested M N (M = N, an outer grid of
+# about M cells) from which the gridded apply and adjoint both beat pxa_nudft in 1, 2 and 3 dimensions at eps = 1e-4
+# and 1e-6 (in one dimension they do from 2^20 on, in two from 2^28; the 3-D apply at eps = 1e-6 still loses at 2^30).
+# T3_PAIRS_PER_CELL: the smallest M N / prod(nf2) among the cells tested at or above that crossover (4854.5, D = 3),
+# rounded up; at M N = 2^30 the chain was not seen to lose on sparser grids, down to 243 pairs per cell.
+# GRID_MAX_CELLS, fine-grid cells per stack row, is a declared guard against a grid nobody asked for, not a
+# measurement; a stack is processed in chunks of rows that stay below it.
+GRID_CROSSOVER_T3 = 1 << 32
+T3_PAIRS_PER_CELL = 4855
+GRID_MAX_CELLS = 1 << 30
+_METHODS = ("auto", "grid", "grid3", "direct")
 
 
 def _as_canonical_coordinate(x):
@@ -77,13 +94,13 @@ def _mesh(N, modeord, dtype):
     return grid
 
 
-def _common(isign, eps, real, enable_warnings, kwargs, cost, gridded=False):
+def _common(isign, eps, real, enable_warnings, kwargs, cost, gridded=False, floor=None):
     modeord = int(kwargs.get("modeord", 0))
     if modeord not in (0, 1):
         raise ValueError(f"modeord must be 0 or 1, got {modeord}.")
     eps, enable_warnings = float(eps), bool(enable_warnings)
     if eps > 0 and enable_warnings and not gridded:
-        msg = _EPS_MSG.format(eps=eps, cost=float(cost), floor=float(GRID_CROSSOVER))
+        msg = _EPS_MSG.format(eps=eps, cost=float(cost), floor=float(GRID_CROSSOVER if floor is None else floor))
         warnings.warn(msg, UserWarning, stacklevel=3)
     return int(np.sign(isign)), bool(real), enable_warnings, modeord
 
@@ -97,6 +114,8 @@ def _method(kwargs):
 
 def _use_grid(method, eps, pairs):
     """Whether a type-1 / type-2 transform of `pairs` = M prod(N) runs on the gridding path."""
+    if method == "grid3":
+        raise ValueError("NUFFT: method='grid3' is the type-3 gridding transform; types 1 and 2 take method='grid'.")
     if method == "grid":
         if not float(eps) > 0:
             raise ValueError("NUFFT: method='grid' needs eps > 0 (eps = 0 is the exact sum, method='direct').")
@@ -114,15 +133,18 @@ def _grid_sigma(upsampfac):
     raise ValueError(f"upsampfac must be 2 or 1.25, got {upsampfac!r}.")
 
 
-def _grid_kernel(eps, sigma):
-    """(w, beta): support in fine-grid cells and shape of phi(z) = exp(beta (sqrt(1 - z^2) - 1))."""
+def _grid_width(eps, sigma):
+    """The width the tolerance asks for, before the clamp to [2, 16]."""
     eps = float(eps)
     guard = 1e-9  # eps = 10^-k gives w = k + 1, whatever the last bit of the logarithm
     if sigma == 2.0:
-        w = math.ceil(-math.log10(eps) + 1 - guard)
-    else:
-        w = math.ceil(-math.log(eps) / (math.pi * math.sqrt(1 - 1 / sigma)) - guard)
-    w = min(max(w, 2), 16)
+        return math.ceil(-math.log10(eps) + 1 - guard)
+    return math.ceil(-math.log(eps) / (math.pi * math.sqrt(1 - 1 / sigma)) - guard)
+
+
+def _grid_kernel(eps, sigma):
+    """(w, beta): support in fine-grid cells and shape of phi(z) = exp(beta (sqrt(1 - z^2) - 1))."""
+    w = min(max(_grid_width(eps, sigma), 2), 16)
     if sigma == 2.0:
         beta = {2: 2.20, 3: 2.26, 4: 2.38}.get(w, 2.30) * w
     else:
@@ -191,6 +213,99 @@ def _grid_plan(x, nf, w, bin_shape, dtype):
     )
 
 
+# ------------------------------------------------------------------ type 3: rescaling and factors (host, float64)
+def _t3_widths(x, z):
+    """Per axis the half-widths and centres (X, C) of the sources and (S, Dc) of the targets, and the safe
+    half-widths (Xs, Ss) with Xs Ss >= 1 (FINUFFT's set_nhg_type3): only one of the two is ever enlarged."""
+    x, z = np.asarray(x, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    X, C = 0.5 * (x.max(axis=0) - x.min(axis=0)), 0.5 * (x.max(axis=0) + x.min(axis=0))
+    S, Dc = 0.5 * (z.max(axis=0) - z.min(axis=0)), 0.5 * (z.max(axis=0) + z.min(axis=0))
+    Xs, Ss = X.copy(), S.copy()
+    for d in range(x.shape[1]):
+        if X[d] == 0 and S[d] == 0:
+            Xs[d] = Ss[d] = 1.0
+        elif X[d] == 0:
+            Xs[d] = 1.0 / S[d]
+        else:
+            Ss[d] = max(S[d], 1.0 / X[d])
+    return dict(X=X, C=C, S=S, Dc=Dc, Xs=Xs, Ss=Ss)
+
+
+def _t3_cells(wd, sigma, w):
+    """Per axis the least length of the outer grid, max(floor(2 sigma Xs Ss / pi + (w + 1)), 2 w) (reference
+    _fft_shape, nufft.py:1932-1947), as floats: the sizes before they are rounded up to FFT lengths, which may be
+    too large to round."""
+    return [max(math.floor(min(2 * sigma * a * b / math.pi + (w + 1), 1e300)), 2 * w)
+            for a, b in zip(wd["Xs"], wd["Ss"])]
+
+
+def _t3_params(x, z, eps, sigma, max_cells=None):
+    """Parameters of the gridded type 3: kernel (w, beta), outer grid nf1, inner fine grid nf2, scale gamma, the
+    centres, and `cells` = prod(nf2).  With `max_cells`, a transform whose fine grid would exceed it gets nf1 = nf2 =
+    None and a lower bound of `cells` (no FFT length is searched for at that size)."""
+    w, beta = _grid_kernel(eps, sigma)
+    wd = _t3_widths(x, z)
+    least = _t3_cells(wd, sigma, w)
+    cells = float(np.prod([math.floor(sigma * n) for n in least]))
+    if max_cells is None or cells <= max_cells:
+        nf1 = tuple(_smooth_even(n) for n in least)
+        nf2 = _grid_size(nf1, sigma, w)
+        cells = int(np.prod(nf2))
+        if max_cells is None or cells <= max_cells:
+            gamma = np.asarray(nf1, dtype=np.float64) / (2 * sigma * wd["Ss"])
+            return dict(wd, w=w, beta=beta, nf1=nf1, nf2=nf2, gamma=gamma, cells=cells)
+    return dict(wd, w=w, beta=beta, nf1=None, nf2=None, gamma=None, cells=cells)
+
+
+def _t3_rescale(x, z, prm):
+    """x' = (x - C) / gamma on the outer grid (|x'| < pi, no footprint wraps) and z' = (z - Dc) gamma 2 pi / nf1,
+    the frequencies of the inner type 2 in radians per outer cell (|z'| <= pi / sigma)."""
+    x, z = np.asarray(x, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    xp = (x - prm["C"]) / prm["gamma"]
+    zp = (z - prm["Dc"]) * prm["gamma"] * 2.0 * np.pi / np.asarray(prm["nf1"], dtype=np.float64)
+    return xp, zp
+
+
+_T3_CHUNK = 4096  # targets per pass of the correction quadrature: a (chunk, _GL_NODES) cosine table
+
+
+def _t3_psi_hat(omega, w, beta, nodes=_GL_NODES):
+    """psi_hat(omega) = (w / 2) int_{-1}^{1} phi(t) cos(omega (w / 2) t) dt, the quadrature of `_grid_correction`
+    at real frequencies omega (radians per cell) in place of k 2 pi / nf."""
+    t, wt = np.polynomial.legendre.leggauss(nodes)
+    t, wt = 0.5 * np.pi * t, 0.5 * np.pi * wt
+    f = np.exp(beta * (np.cos(t) - 1.0)) * np.cos(t) * wt
+    sin_t = np.sin(t)
+    omega = np.asarray(omega, dtype=np.float64)
+    out = np.empty(omega.shape[0])
+    for a in range(0, omega.shape[0], _T3_CHUNK):
+        alpha = omega[a:a + _T3_CHUNK] * (0.5 * w)
+        out[a:a + _T3_CHUNK] = 0.5 * w * (np.cos(alpha[:, None] * sin_t[None, :]) @ f)
+    return out
+
+
+def _t3_factors(x, z, zp, prm):
+    """pre_j = exp(i <Dc, x_j - C>) (M,) and post_k = exp(i <z_k, C>) / prod_d psi_hat(z'_kd) (N,), complex128, for
+    isign = +1 (isign = -1 conjugates them: the correction is real)."""
+    x, z = np.asarray(x, dtype=np.float64), np.asarray(z, dtype=np.float64)
+    pre = np.exp(1j * ((x - prm["C"]) @ prm["Dc"]))
+    corr = np.ones(z.shape[0])
+    for d in range(z.shape[1]):
+        corr /= _t3_psi_hat(zp[:, d], prm["w"], prm["beta"])
+    return pre, np.exp(1j * (z @ prm["C"])) * corr
+
+
+def _t3_width_ok(eps, sigma):
+    """Whether the gridded type 3 can reach `eps`: at upsampling factor 1.25 a width clamped to 16 leaves the error
+    of its two composed approximations far above the tolerance."""
+    return not (sigma == 1.25 and _grid_width(eps, sigma) > 16)
+
+
+def _interleave(c, dtype):
+    """complex (K,) -> (K, 2) real pairs, rounded once to `dtype`."""
+    return np.ascontiguousarray(np.stack([c.real, c.imag], axis=-1).astype(dtype))
+
+
 def _NUFFT12_args(x, N):
     x, N = _as_canonical_coordinate(x), _as_canonical_mode(N)
     if x.shape[-1] == len(N):
@@ -204,7 +319,8 @@ def _NUFFT12_args(x, N):
 
 class NUFFT(pxa.LinOp):
     r"""Non-uniform Fourier transforms of type 1 (non-uniform -> uniform), 2 (uniform -> non-uniform) and 3
-    (non-uniform -> non-uniform) in 1, 2 or 3 dimensions (nufft.py:84-737), evaluated exactly.
+    (non-uniform -> non-uniform) in 1, 2 or 3 dimensions (nufft.py:84-737), evaluated exactly or, with ``eps > 0``
+    and a transform large enough, by gridding to relative accuracy ``eps``.
 
     Complex arrays are real views ``(..., 2 K)`` of interleaved (re, im) pairs; leading dimensions are a stack.
 
@@ -214,9 +330,20 @@ class NUFFT(pxa.LinOp):
     host at construction.  ``"auto"`` grids when ``eps > 0`` and M prod(N) >= ``GRID_CROSSOVER`` and otherwise takes
     the exact sum, with a ``UserWarning`` naming its cost when ``eps > 0``.  ``apply`` and ``adjoint`` of a gridded
     operator are exact adjoints of each other (to rounding, not merely to ``eps``); its ``asarray`` /
-    ``ascomplexarray`` are the exact transform's matrix, which the operator matches to ``eps``.  ``type3`` is always
-    the exact sum.  ``n_trans``, ``plan_fw`` / ``plan_bw`` and the other FINUFFT options are accepted and have no
-    effect.
+    ``ascomplexarray`` are the exact transform's matrix, which the operator matches to ``eps``.
+
+    ``type3`` takes ``method="auto" | "grid3" | "direct"``.  ``"grid3"`` (needs ``eps > 0``) is the gridded type 3:
+    sources and targets are rescaled, the sources spread onto an outer grid, and a type-2 transform of that grid
+    evaluated at the rescaled targets, with a phase factor per source and a phase and correction factor per target.
+    Its grid follows the space-bandwidth product of the two point clouds: above ``GRID_MAX_CELLS`` fine-grid cells
+    ``"grid3"`` is a ``ValueError``, and so is ``upsampfac=1.25`` with an ``eps`` whose kernel width would be
+    clamped (``eps`` below about 1.7e-10).  ``"auto"`` grids when ``eps > 0``, the fine grid has at most
+    ``GRID_MAX_CELLS`` cells and M N >= max(``GRID_CROSSOVER_T3``, ``T3_PAIRS_PER_CELL`` times the cells), and
+    otherwise takes the exact sum with the warning.  ``method="grid"`` on ``type3`` still raises
+    ``NotImplementedError`` and ``"grid3"`` on ``type1`` / ``type2`` is a ``ValueError``: one spelling for both is a
+    follow-up (it changes what an existing test pins).  ``chunked=True`` is not available.
+
+    ``n_trans``, ``plan_fw`` / ``plan_bw`` and the other FINUFFT options are accepted and have no effect.
     """
 
     def __init__(self, shape):
@@ -254,14 +381,37 @@ class NUFFT(pxa.LinOp):
               parallel=False, **kwargs):
         r"""v_k = \sum_j w_j exp(i isign <z_k, x_j>): (..., [2] M) -> (..., 2 N) (nufft.py:550-737)."""
         if bool(chunked):
-            raise NotImplementedError("NUFFT.type3(chunked=True) is not available: the transform is evaluated directly.")
-        if _method(kwargs) == "grid":
-            raise NotImplementedError("NUFFT.type3(method='grid'): the type-3 gridding transform is not built.")
+            raise NotImplementedError("NUFFT.type3(chunked=True) is not available.")
+        method = _method(kwargs)
+        if method == "grid":
+            raise NotImplementedError("NUFFT.type3(method='grid'): the type-3 gridding transform is method='grid3'.")
         x, z = _as_canonical_coordinate(x), _as_canonical_coordinate(z)
         assert x.shape[-1] == z.shape[-1], "x vs. z: dimensionality mis-match."
         kwargs.pop("modeord", None)
-        isign, real, ew, _ = _common(isign, eps, real, enable_warnings, kwargs, x.shape[0] * z.shape[0])
-        return _NUDFT(x, z.astype(x.dtype, copy=False), isign, real, ew)
+        z = z.astype(x.dtype, copy=False)
+        pairs, eps = x.shape[0] * z.shape[0], float(eps)
+        sigma, prm, floor = _grid_sigma(kwargs.get("upsampfac")), None, GRID_CROSSOVER_T3
+        if method == "grid3":
+            if not eps > 0:
+                raise ValueError("NUFFT: method='grid3' needs eps > 0 (eps = 0 is the exact sum, method='direct').")
+            if not _t3_width_ok(eps, sigma):
+                raise ValueError(f"NUFFT.type3: upsampfac=1.25 cannot reach eps={eps:g} on the gridding path (kernel "
+                                 f"width {_grid_width(eps, sigma)} > 16); use upsampfac=2.")
+            prm = _t3_params(x, z, eps, sigma, GRID_MAX_CELLS)
+            if prm["nf2"] is None:
+                raise ValueError(f"NUFFT.type3(method='grid3'): the inner fine grid has at least {prm['cells']:.4g} "
+                                 f"cells, more than GRID_MAX_CELLS = {GRID_MAX_CELLS}: it follows the space-bandwidth "
+                                 "product of the sources and targets.")
+        elif method == "auto" and eps > 0 and pairs >= GRID_CROSSOVER_T3 and _t3_width_ok(eps, sigma):
+            prm = _t3_params(x, z, eps, sigma, GRID_MAX_CELLS)
+            if prm["nf2"] is not None:
+                floor = max(GRID_CROSSOVER_T3, T3_PAIRS_PER_CELL * prm["cells"])
+            if prm["nf2"] is None or pairs < floor:
+                prm = None
+        isign, real, ew, _ = _common(isign, eps, real, enable_warnings, kwargs, pairs, prm is not None, floor)
+        if prm is not None:
+            return _NUFFTGrid3(x, z, isign, real, ew, eps, sigma, prm)
+        return _NUDFT(x, z, isign, real, ew)
 
 
 class _NUDFT(NUFFT):
@@ -396,6 +546,83 @@ class _NUFFTGrid(_NUDFT):
         arr = self._warn_cast(_dev.require(arr, "arr"))
         w, sh = self._stacked(arr, self.codim)
         out = (self._type2 if self._typ == 1 else self._type1)(w, -self._isign)
+        if self._real:
+            out = _dev.complex_real_part(out)
+        return out.reshape(*sh, self.dim)
+
+
+class _NUFFTGrid3(_NUDFT):
+    r"""Type-3 transform of accuracy ``eps``.  With P and R the diagonal factors ``pre`` and ``post``, S_x the
+    spreading matrix of the rescaled sources on the outer grid nf1, C the correction that embeds that grid (its cell
+    l mod nf1 is mode l of the inner type 2, FFT order) in the inner fine grid nf2, F the unnormalised DFT of sign
+    ``isign`` on nf2 and S_z the spreading matrix of the rescaled targets there, the transform is
+    R S_z^T F C S_x P, and its adjoint the transposed chain with the opposite sign and conjugated factors: one plan
+    pair, both kernels, adjoint to rounding.  A stack runs in chunks of rows of at most ``GRID_MAX_CELLS`` fine-grid
+    cells.  Shapes, ``lipschitz``, ``asarray`` / ``ascomplexarray`` (the exact transform's matrix) come from the
+    exact operator."""
+
+    def __init__(self, x, z, isign, real, enable_warnings, eps, sigma, prm=None):
+        super().__init__(x, z, isign, real, enable_warnings)
+        prm = _t3_params(x, z, eps, sigma) if prm is None else prm
+        self._eps, self._sigma, self._prm = float(eps), float(sigma), prm
+        self._w, self._beta, self._nf1, self._nf2 = prm["w"], prm["beta"], prm["nf1"], prm["nf2"]
+        code = 0 if x.dtype == np.float32 else 1
+        bin_shape = _dev.nufft_grid_tiles(code, self._D)[0]
+        xp, zp = _t3_rescale(x, z, prm)
+        pre, post = _t3_factors(x, z, zp, prm)
+        self._plan_x = _grid_plan(xp, self._nf1, self._w, bin_shape, x.dtype)
+        self._plan_z = _grid_plan(zp, self._nf2, self._w, bin_shape, x.dtype)
+        # the factors ride with the sorted points: entry s belongs to point perm[s]
+        self._plan_x["fac"] = _interleave(pre[self._plan_x["perm"]], x.dtype)
+        self._plan_z["fac"] = _interleave(post[self._plan_z["perm"]], x.dtype)
+        self._corr = np.concatenate(
+            [_grid_correction(n, nf, self._w, self._beta) for n, nf in zip(self._nf1, self._nf2)]
+        ).astype(x.dtype)
+        self._plan_dev = None  # uploaded at first use
+
+    def _device_plan(self):
+        if self._plan_dev is None:
+            up = lambda p: tuple(to_device(p[k]) for k in ("l0", "off", "perm", "bin_start", "fac"))  # noqa: E731
+            self._plan_dev = (up(self._plan_x), up(self._plan_z), to_device(self._corr))
+        return self._plan_dev
+
+    def _rows(self, Q):
+        """Stack rows per pass: rows prod(nf2) <= GRID_MAX_CELLS."""
+        return max(1, min(Q, GRID_MAX_CELLS // int(np.prod(self._nf2))))
+
+    def _chain(self, c, forward):
+        """forward: c (Q, 2 M) -> (Q, 2 N); otherwise the transposed chain (Q, 2 N) -> (Q, 2 M)."""
+        (*px, fx), (*pz, fz), corr = self._device_plan()
+        axes, conj = tuple(range(self._D)), (self._isign < 0) == forward
+        out = _dev.empty((c.shape[0], self.codim if forward else 2 * self._src.shape[0]), c)
+        step = self._rows(c.shape[0])
+        for r in range(0, c.shape[0], step):
+            rows = c[r:r + step]
+            if forward:
+                g = _dev.nufft_spread(self._nf1, self._w, self._beta, px, rows, fac=fx, conj=conj)
+                g = _dev.nufft_deconv(self._nf1, self._nf2, 1, True, corr, g)
+                _dev.fft(g, self._nf2, axes, g.shape[0], self._isign > 0, out=g)
+                _dev.nufft_interp(self._nf2, self._w, self._beta, pz, g, out=out[r:r + step], fac=fz, conj=conj)
+            else:
+                g = _dev.nufft_spread(self._nf2, self._w, self._beta, pz, rows, fac=fz, conj=conj)
+                _dev.fft(g, self._nf2, axes, g.shape[0], self._isign < 0, out=g)
+                g = _dev.nufft_deconv(self._nf1, self._nf2, 1, False, corr, g)
+                _dev.nufft_interp(self._nf1, self._w, self._beta, px, g, out=out[r:r + step], fac=fx, conj=conj)
+        return out
+
+    @pxrt.enforce_precision(i="arr")
+    def apply(self, arr):
+        arr = self._warn_cast(_dev.require(arr, "arr"))
+        w, sh = self._stacked(arr, self.dim)
+        if self._real:
+            w = _dev.real_to_complex(w)
+        return self._chain(w, True).reshape(*sh, self.codim)
+
+    @pxrt.enforce_precision(i="arr")
+    def adjoint(self, arr):
+        arr = self._warn_cast(_dev.require(arr, "arr"))
+        w, sh = self._stacked(arr, self.codim)
+        out = self._chain(w, False)
         if self._real:
             out = _dev.complex_real_part(out)
         return out.reshape(*sh, self.dim)
