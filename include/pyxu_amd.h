@@ -669,6 +669,26 @@ int pxa_nufft_interp_fac(int dtype, int D, int64_t Q, int64_t M, const int64_t* 
                          const int32_t* l0, const void* off, const int64_t* perm, const void* grid, void* out,
                          const void* fac, int conj_fac, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Toeplitz convolution: the gram A^H A of a type-2 NUFFT A on n[D] modes (NUFFT.type2(..).gram(), and the cogram
+ * of a type 1), D in {1, 2, 3}.  (A^H A)[k, k'] = t[k - k'] is applied exactly by a circular convolution on
+ * p[d] >= 2 n[d] - 1 cells per axis: out = crop(ifft(khat . fft(pad(in)))), khat (p[0], .., p[D-1]) the real
+ * spectrum of the embedded t with every scaling (1 / prod p) folded in.  Sample i of an axis sits in cell i when
+ * i < split[d] and in cell i + p[d] - n[d] otherwise: split = n keeps the samples contiguous (modes ascending),
+ * split = (n - 1) / 2 + 1 puts the negative modes of FFT order at the top of the line.
+ * Only the non-zero lines are transformed: axes 0 .. D - 2 are expanded one by one (n samples loaded, the zero
+ * cells made in LDS, p results stored), the last axis runs FFT, product and inverse FFT on LDS-resident lines and
+ * stores n samples, and the expanded axes are cropped in reverse (p loaded, n stored): 1, 3 or 5 launches.
+ * in / out (Q, n[0], .., n[D-1]) interleaved complex; out may alias in.  work: pxa_toeplitz_workspace_bytes
+ * bytes (0 for D = 1; Q p0 n1 [n2] plus, for D = 3, Q p0 p1 n2 complex elements).  Every p[d] must have its
+ * prime factors in {2, 3, 5, 7} and be LDS-resident (<= 10240 in fp32, 5120 in fp64) with p[d] >= 2 n[d] - 1, and
+ * 1 <= split[d] <= n[d]: otherwise PXA_ERR_UNSUPPORTED, nothing launched ((size_t)-1 from workspace_bytes).
+ * No allocation, no synchronisation, no atomics: the same call gives the same bits.  Q = 0 does nothing.
+ * ------------------------------------------------------------------------------------------- */
+size_t pxa_toeplitz_workspace_bytes(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* p);
+int pxa_toeplitz_apply(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* p, const int64_t* split,
+                       const void* khat, const void* in, void* out, void* work, void* stream);
+
 /* Measurement hook: with pxa_tuning(PXA_TUNE_PDS_EVENTS, 1), pxa_pds_step / pxa_pds_step_la record HIP
  * events around their kernels (at most 64 steps).  This call waits for the last of them and writes into
  * ms_abc[3] the summed durations of kernels A (axis-0 march; the look-ahead step's priming march, 0 when

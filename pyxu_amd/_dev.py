@@ -1518,4 +1518,35 @@ def nufft_deconv(N, nf, modeord, to_grid, corr, z, out=None):
     return out
 
 
+# ------------------------------------------------------------------ Toeplitz convolution (NUFFT gram)
+def toeplitz_workspace_bytes(dtype_code, Q, n, p):
+    """Workspace of pxa_toeplitz_apply in bytes, or None for lengths outside the fused kernel's envelope (a `p`
+    that is not {2, 3, 5, 7}-smooth, not LDS-resident or below 2 n - 1).  Needs no GPU."""
+    wsz = int(lib.pxa_toeplitz_workspace_bytes(int(dtype_code), len(n), int(Q), i64_array(n), i64_array(p)))
+    return None if wsz == (1 << 64) - 1 else wsz
+
+
+def toeplitz_apply(n, p, split, khat, z, out=None):
+    """out (Q, 2 prod n) = crop(ifft(khat . fft(pad(z)))) on the cells p (pxa_toeplitz_apply): the circular
+    convolution with the real spectrum `khat` (prod p values, every scaling folded in); sample i of axis d sits in
+    cell i (i < split[d]) or i + p[d] - n[d].  `out` may be `z`."""
+    torch = _torch()
+    z, khat = require(z, "z"), require(khat, "khat")
+    Q, cells = z.shape[0], int(np.prod(n))
+    if not (len(n) == len(p) == len(split)) or z.shape[1] != 2 * cells or khat.numel() != int(np.prod(p)) \
+            or khat.dtype != z.dtype:
+        raise ValueError(f"toeplitz_apply: n {tuple(n)}, p {tuple(p)}, split {tuple(split)}, z {tuple(z.shape)}, khat "
+                         f"{tuple(khat.shape)} do not match.")
+    out = empty((Q, 2 * cells), z) if out is None else out
+    if tuple(out.shape) != (Q, 2 * cells) or out.dtype != z.dtype or not out.is_contiguous():
+        raise ValueError(f"toeplitz_apply: out {tuple(out.shape)} {out.dtype} does not match z {tuple(z.shape)}.")
+    wsz = toeplitz_workspace_bytes(dtcode(z), Q, n, p)
+    if wsz is None:
+        check(-3, "pxa_toeplitz_workspace_bytes")  # PXA_ERR_UNSUPPORTED
+    work = torch.empty((wsz,), dtype=torch.uint8, device=z.device) if wsz > 0 else None
+    check(lib.pxa_toeplitz_apply(dtcode(z), len(n), Q, i64_array(n), i64_array(p), i64_array(split), ptr(khat), ptr(z),
+                                 ptr(out), ptr(work) if work is not None else None, stream()), "pxa_toeplitz_apply")
+    return out
+
+
 _tuning_from_env()

@@ -120,6 +120,8 @@ EXPORTS = {
     "pxa_nufft_deconv": (i32, [i32, i32, i64, P_i64, P_i64, i32, i32, vp, vp, vp, vp]),
     "pxa_nufft_spread_fac": (i32, [i32, i32, i64, i64, P_i64, i32, f64, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "pxa_nufft_interp_fac": (i32, [i32, i32, i64, i64, P_i64, i32, f64, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "pxa_toeplitz_workspace_bytes": (sz, [i32, i32, i64, P_i64, P_i64]),
+    "pxa_toeplitz_apply": (i32, [i32, i32, i64, P_i64, P_i64, P_i64, vp, vp, vp, vp, vp]),
     "pxa_pds_kernel_ms": (i32, [vp, i32]),
     "pxa_pds_step": (
         i32,

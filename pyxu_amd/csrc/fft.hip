@@ -1155,6 +1155,221 @@ __global__ void __launch_bounds__(kBlock) complex_real_kernel(int64_t n, const C
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) x[i] = z[i].re;
 }
 
+// ---- Toeplitz (NUFFT gram) convolution: pruned, fused line passes (pxa_toeplitz_apply)
+// A circular convolution of an n-sample axis on P >= 2 n - 1 cells transforms lines that are mostly zero and
+// keeps only n of the P results.  One kernel in three modes, on fft_stockham_kernel's ping-pong buffers and
+// stage<> butterflies (P is any resident {2,3,5,7}-smooth length):
+//   expand: loads the n samples of a line, zero-fills the other cells in LDS, forward FFT_P, stores P cells
+//   fused : loads n, forward FFT_P, times the real spectrum khat[line mod lines_per_row, c], inverse FFT_P,
+//           stores the n mapped cells (the contiguous axis: the padded line never reaches memory)
+//   crop  : loads P cells, inverse FFT_P, stores the n mapped cells
+// Cell map: sample i sits in cell i (i < split) or i + P - n (the negative modes of FFT order at the top).
+enum { kTzExpand = 0, kTzFused = 1, kTzCrop = 2 };
+
+struct TzPlan {
+  int64_t n, P, split;      // samples, cells, first sample mapped to the top of the line
+  int64_t inner, lines;     // stride of the axis (elements), number of lines
+  int64_t n_in, n_out;      // axis length of the source / destination array (n or P)
+  int64_t lines_per_row;    // fused: rows of khat (a line's row is line mod lines_per_row)
+  int lpb;                  // lines per workgroup
+  int nst;
+  int radix[kMaxStages];
+};
+
+// all Stockham stages of nl lines of p.P cells, ping-pong from b0: the result is in b0 after an even number of
+// stages and in b1 after an odd one
+template <typename T, bool INV>
+__device__ __forceinline__ void tz_stages(const TzPlan& p, Cx<T>* b0, Cx<T>* b1, int nl) {
+  const int n = (int)p.P;
+  int ns = 1;
+  for (int s = 0; s < p.nst; ++s) {
+    const int R = p.radix[s];
+    switch (R) {
+      case 8: stage<T, INV, 8>(b0, b1, n, ns, nl); break;
+      case 4: stage<T, INV, 4>(b0, b1, n, ns, nl); break;
+      case 2: stage<T, INV, 2>(b0, b1, n, ns, nl); break;
+      case 3: stage<T, INV, 3>(b0, b1, n, ns, nl); break;
+      case 5: stage<T, INV, 5>(b0, b1, n, ns, nl); break;
+      default: stage<T, INV, 7>(b0, b1, n, ns, nl); break;
+    }
+    ns *= R;
+    __syncthreads();
+    Cx<T>* t = b0;
+    b0 = b1;
+    b1 = t;
+  }
+}
+
+// (line, position) of a workgroup's element i among nl lines of len positions: position-fastest on the
+// contiguous axis, line-fastest on a strided one (adjacent lines are adjacent in memory), as in move_lines
+__device__ inline void tz_coords(int i, int nl, int len, bool contiguous, int& l, int& m) {
+  if (contiguous) {
+    l = i / len;
+    m = i - l * len;
+  } else {
+    m = i / nl;
+    l = i - m * nl;
+  }
+}
+
+template <typename T, int MODE>
+__global__ void __launch_bounds__(kFftThreads) toeplitz_line_kernel(TzPlan p, const Cx<T>* src, Cx<T>* dst,
+                                                                    const T* __restrict__ khat) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  const int n = (int)p.n, P = (int)p.P, split = (int)p.split, gap = P - n;
+  const int64_t line0 = (int64_t)blockIdx.x * p.lpb;
+  const int nl = (int)((p.lines - line0) < p.lpb ? (p.lines - line0) : p.lpb);
+  const bool contiguous = p.inner == 1;
+  Cx<T>* b0 = reinterpret_cast<Cx<T>*>(smem_raw);
+  Cx<T>* b1 = b0 + (size_t)p.lpb * P;
+  // load: every cell of the nl lines is written, the unmapped ones with zero (never read from memory)
+  for (int i = threadIdx.x; i < nl * P; i += kFftThreads) {
+    int l, c;
+    tz_coords(i, nl, P, contiguous, l, c);
+    T re = T(0), im = T(0);  // (a conditionally assigned Cx<double> is left in scratch memory)
+    int m = c;               // crop: the source axis holds all P cells
+    if (MODE != kTzCrop) m = c < split ? c : (c >= split + gap ? c - gap : -1);
+    if (m >= 0) {
+      const Cx<T> a = src[line_base(line0 + l, p.n_in, p.inner) + (int64_t)m * p.inner];
+      re = a.re;
+      im = a.im;
+    }
+    b0[l * P + c] = Cx<T>{re, im};
+  }
+  __syncthreads();
+  auto swap_odd = [&]() {
+    if (p.nst & 1) {
+      Cx<T>* t = b0;
+      b0 = b1;
+      b1 = t;
+    }
+  };
+  if (MODE != kTzCrop) {
+    tz_stages<T, false>(p, b0, b1, nl);
+    swap_odd();
+  }
+  if (MODE == kTzFused) {
+    for (int i = threadIdx.x; i < nl * P; i += kFftThreads) {
+      const int l = i / P, c = i - l * P;
+      const T k = khat[((line0 + l) % p.lines_per_row) * p.P + c];
+      const Cx<T> v = b0[i];
+      b0[i] = Cx<T>{v.re * k, v.im * k};
+    }
+    __syncthreads();
+  }
+  if (MODE != kTzExpand) {
+    tz_stages<T, true>(p, b0, b1, nl);
+    swap_odd();
+  }
+  // store: expand all P cells, otherwise the n mapped ones
+  const int len = MODE == kTzExpand ? P : n;
+  for (int i = threadIdx.x; i < nl * len; i += kFftThreads) {
+    int l, m;
+    tz_coords(i, nl, len, contiguous, l, m);
+    const int c = MODE == kTzExpand ? m : (m < split ? m : m + gap);
+    dst[line_base(line0 + l, p.n_out, p.inner) + (int64_t)m * p.inner] = b0[l * P + c];
+  }
+}
+
+template <typename T, int MODE>
+int launch_toeplitz(TzPlan p, const Cx<T>* src, Cx<T>* dst, const T* khat, hipStream_t st) {
+  FftPlan f;
+  if (!factor(p.P, f)) return PXA_ERR_UNSUPPORTED;
+  p.nst = f.nst;
+  for (int s = 0; s < f.nst; ++s) p.radix[s] = f.radix[s];
+  p.n_in = MODE == kTzCrop ? p.P : p.n;
+  p.n_out = MODE == kTzExpand ? p.P : p.n;
+  const size_t line_bytes = (size_t)p.P * sizeof(Cx<T>);
+  int lpb = (int)(kFftLds / (2 * line_bytes));  // launch_stockham's rule
+  if (lpb > 16) lpb = 16;
+  if (lpb < 1) lpb = 1;
+  if (p.inner > 1 && lpb > p.inner) lpb = (int)p.inner;
+  p.lpb = lpb;
+  const int64_t blocks = (p.lines + lpb - 1) / lpb;
+  PXA_CHECK_ARG(blocks <= 0x7fffffff);
+  const size_t smem = 2 * (size_t)lpb * line_bytes;
+  if (smem > kFftLdsMax) return PXA_ERR_UNSUPPORTED;
+  static bool attr = false;  // per instantiation
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)toeplitz_line_kernel<T, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kFftLdsMax);
+    attr = true;
+  }
+  hipLaunchKernelGGL((toeplitz_line_kernel<T, MODE>), dim3((unsigned)blocks), dim3(kFftThreads), smem, st, p, src, dst,
+                     khat);
+  return last_launch_status();
+}
+
+// D in {1, 2, 3}, n >= 1, p >= 2 n - 1 smooth and resident, 1 <= split <= n, Q >= 0, and every array below 2^62
+// elements; PXA_ERR_ARG for malformed arguments, PXA_ERR_UNSUPPORTED for a length outside the envelope
+template <typename T>
+int toeplitz_check(int D, int64_t Q, const int64_t* n, const int64_t* p, const int64_t* split) {
+  PXA_CHECK_ARG(D >= 1 && D <= 3 && Q >= 0 && n && p);
+  double cells = (double)(Q > 0 ? Q : 1);
+  for (int d = 0; d < D; ++d) {
+    PXA_CHECK_ARG(n[d] >= 1 && p[d] >= 1);
+    if (p[d] < 2 * n[d] - 1 || !stockham_fits<T>(p[d])) return PXA_ERR_UNSUPPORTED;
+    if (split && (split[d] < 1 || split[d] > n[d])) return PXA_ERR_UNSUPPORTED;
+    cells *= (double)p[d];
+  }
+  if (cells >= 4.0e18) return PXA_ERR_UNSUPPORTED;
+  return PXA_OK;
+}
+
+// complex elements of the two workspaces: (Q, p0, n1[, n2]) and, for D = 3, (Q, p0, p1, n2)
+inline void toeplitz_work_elems(int D, int64_t Q, const int64_t* n, const int64_t* p, int64_t& wa, int64_t& wb) {
+  wa = wb = 0;
+  if (D == 2) wa = Q * p[0] * n[1];
+  if (D == 3) {
+    wa = Q * p[0] * n[1] * n[2];
+    wb = Q * p[0] * p[1] * n[2];
+  }
+}
+
+template <typename T>
+int toeplitz_entry(int D, int64_t Q, const int64_t* n, const int64_t* p, const int64_t* split, const void* khat,
+                   const void* in, void* out, void* work, hipStream_t st) {
+  const int c = toeplitz_check<T>(D, Q, n, p, split);
+  if (c != PXA_OK) return c;
+  PXA_CHECK_ARG(split != nullptr);
+  if (Q == 0) return PXA_OK;
+  PXA_CHECK_ARG(khat && in && out && (D == 1 || work));
+  int64_t wa, wb;
+  toeplitz_work_elems(D, Q, n, p, wa, wb);
+  const Cx<T>* x = (const Cx<T>*)in;
+  Cx<T>* y = (Cx<T>*)out;
+  Cx<T>* A = (Cx<T>*)work;
+  Cx<T>* B = A + wa;
+  const T* k = (const T*)khat;
+  // one pass along axis a of an array whose axes after a have `inner` elements and whose other axes make `lines`
+  auto pass = [&](auto mode, int a, int64_t inner, int64_t lines, const Cx<T>* s, Cx<T>* d) {
+    TzPlan t;
+    t.n = n[a];
+    t.P = p[a];
+    t.split = split[a];
+    t.inner = inner;
+    t.lines = lines;
+    t.lines_per_row = 1;
+    for (int b = 0; b < D - 1; ++b) t.lines_per_row *= p[b];
+    return launch_toeplitz<T, mode()>(t, s, d, k, st);
+  };
+  using Ex = std::integral_constant<int, kTzExpand>;
+  using Fu = std::integral_constant<int, kTzFused>;
+  using Cr = std::integral_constant<int, kTzCrop>;
+  int e;
+  if (D == 1) return pass(Fu{}, 0, 1, Q, x, y);
+  if (D == 2) {
+    if ((e = pass(Ex{}, 0, n[1], Q * n[1], x, A))) return e;
+    if ((e = pass(Fu{}, 1, 1, Q * p[0], A, A))) return e;
+    return pass(Cr{}, 0, n[1], Q * n[1], A, y);
+  }
+  if ((e = pass(Ex{}, 0, n[1] * n[2], Q * n[1] * n[2], x, A))) return e;
+  if ((e = pass(Ex{}, 1, n[2], Q * p[0] * n[2], A, B))) return e;
+  if ((e = pass(Fu{}, 2, 1, Q * p[0] * p[1], B, B))) return e;
+  if ((e = pass(Cr{}, 1, n[2], Q * p[0] * n[2], B, A))) return e;
+  return pass(Cr{}, 0, n[1] * n[2], Q * n[1] * n[2], A, y);
+}
+
 }  // namespace
 }  // namespace pxa
 
@@ -1218,6 +1433,21 @@ int pxa_complex_real_part(int dtype, int64_t n, const void* z, void* x, void* st
                        (const Cx<T>*)z, (T*)x);
     return last_launch_status();
   });
+}
+
+size_t pxa_toeplitz_workspace_bytes(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* p) {
+  int c = PXA_ERR_DTYPE;
+  if (dtype == PXA_F32) c = toeplitz_check<float>(D, Q, n, p, nullptr);
+  else if (dtype == PXA_F64) c = toeplitz_check<double>(D, Q, n, p, nullptr);
+  if (c != PXA_OK) return (size_t)-1;
+  int64_t wa, wb;
+  toeplitz_work_elems(D, Q, n, p, wa, wb);
+  return (size_t)(wa + wb) * (dtype == PXA_F32 ? sizeof(Cx<float>) : sizeof(Cx<double>));
+}
+
+int pxa_toeplitz_apply(int dtype, int D, int64_t Q, const int64_t* n, const int64_t* p, const int64_t* split,
+                       const void* khat, const void* in, void* out, void* work, void* stream) {
+  PXA_DISPATCH(dtype, T, return toeplitz_entry<T>(D, Q, n, p, split, khat, in, out, work, as_stream(stream)));
 }
 
 }  // extern "C"

@@ -360,7 +360,7 @@ class NUFFT(pxa.LinOp):
         grid = _mesh(N, modeord, x.dtype).reshape(-1, x.shape[1])
         if gridded:
             return _NUFFTGrid(1, x, grid, isign, real, ew, N, modeord, eps, sigma)
-        return _NUDFT(x, grid, isign, real, ew, mode=N, modeord=modeord)
+        return _NUDFT(x, grid, isign, real, ew, mode=N, modeord=modeord, typ=1)
 
     @staticmethod
     @pxrt.enforce_precision(i="x", o=False, allow_None=False)
@@ -373,7 +373,7 @@ class NUFFT(pxa.LinOp):
         grid = _mesh(N, modeord, x.dtype).reshape(-1, x.shape[1])
         if gridded:
             return _NUFFTGrid(2, x, grid, isign, real, ew, N, modeord, eps, sigma)
-        return _NUDFT(grid, x, isign, real, ew, mode=N, modeord=modeord)
+        return _NUDFT(grid, x, isign, real, ew, mode=N, modeord=modeord, typ=2)
 
     @staticmethod
     @pxrt.enforce_precision(i=("x", "z"), o=False, allow_None=False)
@@ -418,8 +418,9 @@ class _NUDFT(NUFFT):
     r"""out_n = \sum_m w_m exp(i isign <src_m, tgt_n>): (..., [2] M) -> (..., 2 N).  With ``real`` the input of
     ``apply`` (and the output of ``adjoint``) is real-valued."""
 
-    def __init__(self, src, tgt, isign, real, enable_warnings, mode=None, modeord=0):
+    def __init__(self, src, tgt, isign, real, enable_warnings, mode=None, modeord=0, typ=3):
         self._src, self._tgt = src, tgt  # host (M, D) / (N, D), one dtype
+        self._typ = int(typ)
         self._isign = int(isign)
         self._real = bool(real)
         self._enable_warnings = bool(enable_warnings)
@@ -490,6 +491,27 @@ class _NUDFT(NUFFT):
         dtype = pxrt.getPrecision().value if dtype is None else dtype
         return _mesh(self._mode, self._modeord, dtype)
 
+    def _generic_normal(self, which, weights, eps, fused):
+        if not (weights is None and eps is None and fused is None):
+            raise ValueError(f"NUFFT.{which}(): weights / eps / fused belong to the Toeplitz form (gram of a type-2, "
+                             "cogram of a complex type-1 transform); this operator has the generic product only.")
+        return getattr(pxa.LinOp, which)(self)
+
+    def gram(self, weights=None, eps=None, fused=None):
+        r"""A^H A.  For a type-2 transform the Toeplitz operator :py:class:`_NUFFTGram` (A^H diag(weights) A with
+        ``weights``); otherwise the generic product ``A.T * A``."""
+        if self._typ == 2:
+            return _NUFFTGram(self, self._isign, self._real, weights, eps, fused)
+        return self._generic_normal("gram", weights, eps, fused)
+
+    def cogram(self, weights=None, eps=None, fused=None):
+        r"""A A^H.  A type-1 transform of sign s is the adjoint of the type 2 of sign -s, so its cogram is that
+        transform's Toeplitz gram (not with ``real=True``, whose adjoint drops the imaginary part between the two
+        factors); otherwise the generic product ``A * A.T``."""
+        if self._typ == 1 and not self._real:
+            return _NUFFTGram(self, -self._isign, False, weights, eps, fused)
+        return self._generic_normal("cogram", weights, eps, fused)
+
 
 class _NUFFTGrid(_NUDFT):
     r"""Type-1 / type-2 transform of accuracy ``eps`` on the oversampled grid.  With S the spreading matrix of the
@@ -500,8 +522,8 @@ class _NUFFTGrid(_NUDFT):
 
     def __init__(self, typ, x, grid, isign, real, enable_warnings, N, modeord, eps, sigma):
         src, tgt = (x, grid) if typ == 1 else (grid, x)
-        super().__init__(src, tgt, isign, real, enable_warnings, mode=N, modeord=modeord)
-        self._typ, self._eps, self._sigma = int(typ), float(eps), float(sigma)
+        super().__init__(src, tgt, isign, real, enable_warnings, mode=N, modeord=modeord, typ=typ)
+        self._eps, self._sigma = float(eps), float(sigma)
         self._w, self._beta = _grid_kernel(eps, sigma)
         self._nf = _grid_size(N, sigma, self._w)
         code = 0 if x.dtype == np.float32 else 1
@@ -590,6 +612,13 @@ class _NUFFTGrid3(_NUDFT):
         """Stack rows per pass: rows prod(nf2) <= GRID_MAX_CELLS."""
         return max(1, min(Q, GRID_MAX_CELLS // int(np.prod(self._nf2))))
 
+    # the normal operators of a type 3 are not Toeplitz: the generic products, whatever _NUDFT overrides
+    def gram(self):
+        return pxa.LinOp.gram(self)
+
+    def cogram(self):
+        return pxa.LinOp.cogram(self)
+
     def _chain(self, c, forward):
         """forward: c (Q, 2 M) -> (Q, 2 N); otherwise the transposed chain (Q, 2 N) -> (Q, 2 M)."""
         (*px, fx), (*pz, fz), corr = self._device_plan()
@@ -623,6 +652,145 @@ class _NUFFTGrid3(_NUDFT):
         arr = self._warn_cast(_dev.require(arr, "arr"))
         w, sh = self._stacked(arr, self.codim)
         out = self._chain(w, False)
+        if self._real:
+            out = _dev.complex_real_part(out)
+        return out.reshape(*sh, self.dim)
+
+
+# ------------------------------------------------------------------ Toeplitz gram of a type-2 transform
+# Longest line the fused kernel keeps in LDS (pxa_toeplitz_apply: two buffers of complex cells in 160 KB).
+_TOEPLITZ_RESIDENT = {np.dtype(np.float32): 10240, np.dtype(np.float64): 5120}
+# fused=None in two and three dimensions: the fused kernel up to this many cells per axis, the length at which a
+# workgroup still holds 4 lines (64 KB of LDS for two buffers).  Measured in fp32 (scripts/bench_nufft_gram.py, DESIGN.md
+# §8k): against the chain of existing kernels it wins at P = 512 and 1024 and loses at 2048 (2 lines, by 3 %) and 4096
+# (1 line, by 19 %), where the in-place power-of-two FFT kernel behind the chain holds more lines of a strided axis.
+# The fp64 figure is the same line count, not a measurement.  One dimension is a single launch and wins at 8192.
+_TOEPLITZ_BEST = {np.dtype(np.float32): 1024, np.dtype(np.float64): 512}
+# The spectrum of the embedded kernel is real because t[-d] = conj(t[d]); what the transform leaves in the imaginary
+# part is its own rounding: for an FFT of prod(P) cells an error of about u sqrt(log2 prod P) ||t||_2 per cell, and
+# max |spectrum| >= rms(spectrum) = ||t||_2 (Parseval).  1024 u (u the unit roundoff of the working precision)
+# leaves two orders of magnitude for log factors and the asymmetry of t's own rounding; a kernel that is not
+# Hermitian misses it by many orders.
+_KHAT_IMAG_TOL = 1024.0
+
+
+def _toeplitz_sizes(N, modeord):
+    """Per axis the cells P = _smooth_even(2 n - 1) of the circular convolution and the split of the cell map
+    (sample i in cell i when i < split, else in cell i + P - n): n for ascending modes, (n - 1) // 2 + 1 for FFT
+    order (the negative modes at the top)."""
+    P = tuple(_smooth_even(2 * n - 1) for n in N)
+    split = tuple(n if modeord == 0 else (n - 1) // 2 + 1 for n in N)
+    return P, split
+
+
+class _NUFFTGram(pxa.SelfAdjointOp):
+    r"""G = A^H diag(w) A of a type-2 transform A (sign ``isign``, modes N, points x): the multilevel Toeplitz matrix
+    G[n, n'] = t[n - n'], t[d] = \sum_j w_j exp(-i isign <d, x_j>), applied exactly as a circular convolution on
+    P_d = _smooth_even(2 N_d - 1) cells per axis: zero-pad, FFT, multiply by the real spectrum ``khat`` of the
+    embedded t, inverse FFT, crop.  t is one type-1 transform of the weights onto 2 N - 1 modes, evaluated once at
+    the first ``apply`` (exactly with ``eps = 0``, else by gridding to ``eps``); after that no non-uniform point is
+    touched, and the cost of an ``apply`` depends on N alone.
+
+    ``fused=True`` runs pxa_toeplitz_apply (pruned line passes, the last axis fused in LDS); ``fused=False`` the
+    chain of existing kernels (embed, FFT, product, inverse FFT, extract) on the full padded grid, which serves any
+    length; ``fused=None`` takes the faster of the two as measured (``_TOEPLITZ_BEST``).  They agree to rounding.
+    With ``real`` the operator acts on real vectors of length prod N."""
+
+    def __init__(self, parent, isign, real, weights=None, eps=None, fused=None):
+        x = parent._tgt if parent._typ == 2 else parent._src
+        N = tuple(int(n) for n in parent._mode)
+        M, cells = x.shape[0], int(np.prod(N))
+        super().__init__(shape=(cells if real else 2 * cells,) * 2)
+        self._x, self._N, self._isign, self._real = x, N, int(isign), bool(real)
+        self._src, self._enable_warnings = x, parent._enable_warnings  # (_warn_cast)
+        self._modeord = parent._modeord
+        if weights is not None:
+            weights = to_NUMPY(weights) if is_device_array(weights) else np.asarray(weights)
+            if np.iscomplexobj(weights) or weights.dtype.kind not in "fiu":
+                raise ValueError(f"NUFFT.gram(weights=...): real weights expected, got {weights.dtype}.")
+            if weights.shape != (M,):
+                raise ValueError(f"NUFFT.gram(weights=...): expected shape ({M},), got {weights.shape}.")
+            weights = np.ascontiguousarray(weights, dtype=x.dtype)
+        self._weights = weights
+        self._eps = float(getattr(parent, "_eps", 0.0) if eps is None else eps)
+        if not self._eps >= 0:
+            raise ValueError(f"NUFFT.gram(eps=...): eps >= 0 expected, got {eps!r}.")
+        self._sigma = getattr(parent, "_sigma", 2.0)
+        self._P, self._split = _toeplitz_sizes(N, self._modeord)
+        resident = max(self._P) <= _TOEPLITZ_RESIDENT[np.dtype(x.dtype)]
+        if fused and not resident:
+            raise ValueError(f"NUFFT.gram(fused=True): the padded lengths {self._P} exceed the "
+                             f"{_TOEPLITZ_RESIDENT[np.dtype(x.dtype)]} cells the fused kernel keeps in LDS.")
+        best = resident and (len(N) == 1 or max(self._P) <= _TOEPLITZ_BEST[np.dtype(x.dtype)])
+        self._fused = best if fused is None else bool(fused)
+        self._khat = self._khat_c = self._ones = None  # device plan, built at first use
+        self.lipschitz = float(M if weights is None else np.abs(weights.astype(np.float64)).sum()) * cells
+
+    _warn_cast = _NUDFT._warn_cast
+    _stacked = _NUDFT._stacked
+
+    def _plan(self):
+        """khat (prod P, real, 1 / prod P folded in) on the device."""
+        if self._khat is not None:
+            return self._khat
+        x, N, P, D = self._x, self._N, self._P, len(self._N)
+        n2 = tuple(2 * n - 1 for n in N)  # modes d = -(n - 1) .. n - 1, ascending
+        with pxrt.Precision(pxrt.Width(x.dtype)):
+            kw = dict(method="grid", upsampfac=self._sigma) if self._eps > 0 else dict(method="direct")
+            psf = NUFFT.type1(x, n2, isign=-self._isign, eps=self._eps, real=True, enable_warnings=False, **kw)
+            w = np.ones(x.shape[0], dtype=x.dtype) if self._weights is None else self._weights
+            with pxrt.EnforcePrecision(False):
+                t = psf.apply(to_device(w.reshape(1, -1)))
+        ones = to_device(np.ones(sum(n2), dtype=x.dtype))
+        g = _dev.nufft_deconv(n2, P, 0, True, ones, t)  # t[d] in cell d mod P
+        _dev.fft(g, P, tuple(range(D)), 1, False, out=g)
+        spec = to_NUMPY(g).reshape(-1, 2)  # one-off: the check below reads every cell
+        top = float(np.abs(spec[:, 0]).max())
+        imag = float(np.abs(spec[:, 1]).max())
+        if not imag <= _KHAT_IMAG_TOL * np.finfo(x.dtype).eps * top:
+            raise RuntimeError(f"NUFFT gram: the spectrum of the Toeplitz kernel is not real (max |Im| = {imag:.3e} "
+                               f"against max |Re| = {top:.3e}): the kernel t is not Hermitian.")
+        self._khat = to_device(np.ascontiguousarray(spec[:, 0] / float(np.prod(P)), dtype=x.dtype))
+        return self._khat
+
+    def _rows(self, Q):
+        """Stack rows per pass: the pass's workspace stays below GRID_MAX_CELLS cells."""
+        N, P = self._N, self._P
+        if not self._fused:
+            cells = int(np.prod(P))
+        elif len(N) == 1:
+            cells = N[0]
+        else:  # (P0, N1[, N2]) and, in three dimensions, (P0, P1, N2)
+            cells = P[0] * N[-1] * (1 if len(N) == 2 else N[1] + P[1])
+        return max(1, min(Q, GRID_MAX_CELLS // cells))
+
+    def _fallback(self, u, out):
+        """The same convolution from existing kernels, on the full padded grid (mode k in cell k mod P: a cyclic
+        shift of the fused kernel's placement, so the same khat serves)."""
+        N, P, axes = self._N, self._P, tuple(range(len(self._N)))
+        if self._khat_c is None:
+            self._khat_c = _dev.real_to_complex(self._khat.reshape(1, -1))
+            self._ones = to_device(np.ones(sum(N), dtype=self._x.dtype))
+        g = _dev.nufft_deconv(N, P, self._modeord, True, self._ones, u)
+        _dev.fft(g, P, axes, g.shape[0], False, out=g)
+        _dev.complex_mul(g, self._khat_c, out=g)
+        _dev.fft(g, P, axes, g.shape[0], True, out=g)
+        return _dev.nufft_deconv(N, P, self._modeord, False, self._ones, g, out=out)
+
+    @pxrt.enforce_precision(i="arr")
+    def apply(self, arr):
+        arr = self._warn_cast(_dev.require(arr, "arr"))
+        u, sh = self._stacked(arr, self.dim)
+        if self._real:
+            u = _dev.real_to_complex(u)
+        khat = self._plan()
+        out = _dev.empty(tuple(u.shape), u)
+        step = self._rows(u.shape[0])
+        for r in range(0, u.shape[0], step):
+            if self._fused:
+                _dev.toeplitz_apply(self._N, self._P, self._split, khat, u[r:r + step], out=out[r:r + step])
+            else:
+                self._fallback(u[r:r + step], out[r:r + step])
         if self._real:
             out = _dev.complex_real_part(out)
         return out.reshape(*sh, self.dim)
