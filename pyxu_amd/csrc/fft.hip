@@ -647,8 +647,9 @@ __global__ void __launch_bounds__(TH, 4) fft_lds_kernel(FftPlan p, const Cx<T>* 
       // was followed at once by `v_add_u32 v0, ...` (the next LDS address) into its data register v0, and now
       // and then the low dword of an fp64 result was that address (round-4 / r05b failure of
       // test_fft_vs_numpy[(2048, 2048)-(0, 1)-float64-True]: 16 values in one row, low dwords 0xd940..0xdc30,
-      // high dwords exact; tests/test_gpu_fft.py::test_fft_f64_store_hazard_pattern).  8-B stores (fp32) have
-      // no such hazard and keep the SGPR offset.
+      // high dwords exact; tests/test_isa_hazards.py and, against the generic path bit for bit,
+      // tests/test_gpu_fft_paths.py::test_fft_fast_path_equals_generic_bitwise).  8-B stores (fp32) have no such
+      // hazard and keep the SGPR offset.
       for (int k = 0; k < PER; ++k) {
         if constexpr (sizeof(Cx<T>) > 8) cx_buf_st<T>(buf[slot(k)], rs, voff + k * sstep, 0);
         else cx_buf_st<T>(buf[slot(k)], rs, voff, k * sstep);
@@ -728,7 +729,7 @@ bool smooth(int64_t n) {
 
 // One workgroup may take the whole LDS for a single long line; several lines per workgroup share 64 KB
 // (two workgroups per CU).
-constexpr size_t kFftLdsMax = 160 * 1024;
+constexpr size_t kFftLdsMax = 160 * 1024;  // (tests/_fft_paths.py mirrors the dispatch below: change both)
 constexpr int64_t kDirectMaxN = 8 * kFftThreads;
 
 template <typename T>

@@ -9,6 +9,7 @@ relative 1e-5 (fp32) / 1e-12 (fp64).
 import numpy as np
 import pytest
 
+from _fft_diag import _diagnose
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -44,49 +45,10 @@ EXTRA_CASES = [
     # beyond one workgroup's LDS: four-step (smooth) and Bluestein (any length), contiguous and strided
     ((16384,), None, (16384,), (0,)),  # 2^14 = 128 x 128 four-step
     ((12000, 3), (0,), (12000, 3), (0,)),  # smooth, strided axis
-    ((4099,), None, (4099,), (0,)),  # prime > 2048: Bluestein with m = 8192
+    ((4099,), None, (4099,), (0,)),  # prime > 2048: Bluestein with m = 16384
     ((3, 2053), (1,), (3, 2053), (1,)),  # prime just above the direct-DFT envelope
     ((2, 2*3001), None, (2, 6002), (0, 1)),  # 2 x 3001: Bluestein on a non-smooth composite
 ]
-
-
-def _diagnose(got, want, sh, rerun):
-    """Failure report: where the wrong elements are (flat index -> (stack, *arg_shape) coordinates of the
-    complex element), how wrong (relative to the array's rms, and in ulps of T), and whether the same call,
-    run again, gives the same bits.  Written to the assertion message and, with PXA_FAIL_DIR set, to an .npz
-    (round-4 verdict: a one-off 4e-10 fp64 failure was lost for want of this)."""
-    import os
-
-    got = np.asarray(got)
-    want = np.asarray(want, dtype=got.dtype)
-    err = np.abs(got.astype(np.float64) - want.astype(np.float64))
-    rms = float(np.sqrt(np.mean(want.astype(np.float64) ** 2))) or 1.0
-    tol = 64 * np.finfo(got.dtype).eps * rms
-    bad = np.flatnonzero(err.ravel() > tol)
-    again = np.asarray(rerun())
-    lines = [f"{bad.size} of {err.size} elements off by > 64 eps rms; max {err.max() / rms:.3e} rms",
-             f"rerun bit-identical to the failing call: {np.array_equal(again, got)}; "
-             f"rerun rel err {np.linalg.norm(again - want) / np.linalg.norm(want):.3e}"]
-    if bad.size:
-        cplx = got.shape[-1] != int(np.prod(sh))  # interleaved (re, im) view
-        el = bad // 2 if cplx else bad
-        coords = np.stack(np.unravel_index(el, (got.shape[0], *sh)), axis=1)
-        for ax in range(coords.shape[1]):
-            u = np.unique(coords[:, ax])
-            lines.append(f"axis {ax - 1 if ax else 'stack'}: {u.size} distinct values, first {u[:8].tolist()}")
-        lines.append(f"first bad flat indices {bad[:16].tolist()}")
-        fg, fw = got.ravel()[bad[:16]], want.ravel()[bad[:16]]
-        lines.append(f"got {fg.tolist()} want {fw.tolist()}")
-        if got.dtype == np.float64:
-            xor = fg.view(np.uint64) ^ fw.view(np.uint64)
-            lines.append("xor bits " + " ".join(f"{int(v):016x}" for v in xor))
-    out = os.environ.get("PXA_FAIL_DIR")
-    if out:
-        os.makedirs(out, exist_ok=True)
-        keep = bad[:4096]  # the wrong elements only (a whole 2048^2 pair would not travel back)
-        np.savez(os.path.join(out, f"fft_fail_{'x'.join(map(str, sh))}_{got.dtype}.npz"), bad=keep,
-                 got=got.ravel()[keep], want=want.ravel()[keep], again=again.ravel()[keep])
-    return "\n".join(lines)
 
 
 def _check(got, want, tol, sh, rerun):
