@@ -275,6 +275,35 @@ int pxa_cg_update_tail(int dtype, int64_t rows, int64_t n, void* x, void* r, voi
 int pxa_cg_update_xr(int dtype, int64_t rows, int64_t n, void* x, void* r, const void* p, const void* ap, const double* rr,
                      void* work, void* stream);
 
+/* NLCG direction update after g1 = grad f(x_{k+1}) (opt/solver/nlcg.py:213-227 and __compute_beta :254-265), for
+ * `rows` stacked problems of n entries, in two launches: per-block partials of sum g1^2 and (variant 1) of
+ * sum g1 (g1 - g0), the difference formed in the working type and the product and sum in double; then
+ *   beta = (T)(sum g1^2 / gg0)                          variant 0, Fletcher-Reeves
+ *   beta = (T)max(0, sum g1 (g1 - g0) / gg0)            variant 1, Polak-Ribiere+ (a NaN ratio stays NaN)
+ *   beta = 0                                            restart != 0 (nlcg.py:215-216; g0 may then be NULL)
+ * p_new = beta p - g1 (out of place: p_new aliases neither p nor g1) and the per-block partials of <g1, p_new>,
+ * which the next line search needs (math/linesearch.py:72).  gg0: sum g0^2 per row as published by the previous
+ * call (device double); a plain IEEE division, so gg0 == 0 gives inf / NaN as in the reference.  gg_out (device,
+ * != gg0) and gg_host / flags / seq receive sum g1^2 exactly as rr_out / rr_host / flags / seq of pxa_cg_update.
+ * `work`: pxa_nlcg_workspace_bytes(rows) bytes = three planes of rows * 64 doubles; on return the third plane
+ * (work + rows * 128 doubles) holds the <g1, p_new> partials, row r's at [r * nb, (r + 1) * nb) with
+ * nb = min(64, ceil(n / 256)), for pxa_ls_armijo.  Partition and fold order of pxa_cg_update, no atomics:
+ * the same bits run to run.  rows <= 65535. */
+size_t pxa_nlcg_workspace_bytes(int64_t rows);
+int pxa_nlcg_direction(int dtype, int variant, int restart, int64_t rows, int64_t n, const void* g1, const void* g0,
+                       const void* p, void* p_new, const double* gg0, double* gg_out, double* gg_host, uint32_t* flags,
+                       uint32_t seq, void* work, void* stream);
+
+/* Armijo test of one backtracking trial for every row (math/linesearch.py:71-93), one launch of one workgroup,
+ * one wavefront per row in turn: d_f = (T)c (T)<g, p>, rhs = f_x + a d_f (product, then sum, each rounded to T, never
+ * contracted), fail = f_trial > rhs (a NaN on either side is no failure, as `lhs > rhs` in the reference); on fail
+ * a[row] *= (T)r and trials[row] += 1 (device int32).  gp: with nb > 0 the nb partials per row left by
+ * pxa_nlcg_direction (folded in its fixed order), with nb == 0 one folded double per row (pxa_row_reduce).
+ * The number of failing rows goes to *nfail_host, then `seq` to *flag (both pxa_host_alloc memory, system-scope
+ * release): the reference's `.any()` as one four-byte host read.  rows <= 65535. */
+int pxa_ls_armijo(int dtype, int64_t rows, const void* f_trial, const void* f_x, const double* gp, int32_t nb, double c,
+                  double r, void* a, int32_t* trials, uint32_t* nfail_host, uint32_t* flag, uint32_t seq, void* stream);
+
 /* RelError statistics from the fused PGD step's per-tile partials (pxa_pgd_tv2d_step[_y] with
  * `partials`): out[0 * rows + r] = sum (x_new - x)^2 and out[1 * rows + r] = sum x^2 over the per_row
  * consecutive tiles of stack row r, fixed summation order.  At stop_rate 1 the criterion's stored x_prev

@@ -613,6 +613,103 @@ def cg_update_xr(x, r, p, ap, rr, work):
                                stream()), "pxa_cg_update_xr")
 
 
+NLCG_FR, NLCG_PR = 0, 1  # pxa_nlcg_direction variants
+_CG_BLOCKS = 64  # partials per row of the CG / NLCG tail partition (csrc/common.hpp kCgBlocks)
+
+
+def nlcg_blocks(n):
+    """Partials per row that pxa_nlcg_direction leaves for pxa_ls_armijo: min(64, ceil(n / 256))."""
+    return min(_CG_BLOCKS, (int(n) + 255) // 256)
+
+
+def nlcg_gp_partials(work, rows):
+    """The <g1, p_new> partials plane of a pxa_nlcg_direction workspace (float64 device tensor `work`)."""
+    return work[2 * rows * _CG_BLOCKS: 3 * rows * _CG_BLOCKS]
+
+
+def nlcg_direction(variant, restart, g1, g0, p, p_new, gg0, gg_out, gg_host, work):
+    """pxa_nlcg_direction on (rows, n) g1 / g0 / p -> p_new = beta p - g1 (out of place), beta from `variant`
+    (NLCG_FR / NLCG_PR), this step's g1, the previous g0 (None allowed for FR or a restart) and gg0 = sum g0^2
+    (device float64 (rows,)); sum g1^2 lands in gg_out (device, not gg0) and in gg_host (a
+    HostFlagBuffer(rows, rows, rows): returns the publication's sequence number; a pinned tensor; or None).
+    `work`: float64 device tensor of pxa_nlcg_workspace_bytes(rows) bytes; nlcg_gp_partials(work, rows) then
+    holds the <g1, p_new> partials."""
+    torch = _torch()
+    g1, p = require(g1, "g1"), require(p, "p")
+    if not require(p_new, "p_new") is p_new:
+        raise ValueError("nlcg_direction: p_new is written in place and must be contiguous")
+    if g1.dim() != 2 or p.shape != g1.shape or p_new.shape != g1.shape or p.dtype != g1.dtype or p_new.dtype != g1.dtype:
+        raise ValueError("nlcg_direction: g1, p and p_new must be (rows, n) tensors of one dtype")
+    rows, n = g1.shape
+    if not (1 <= rows <= 65535 and n >= 1):
+        raise ValueError(f"nlcg_direction: rows must be in [1, 65535] and n >= 1, got {(rows, n)}")
+    if variant not in (NLCG_FR, NLCG_PR):
+        raise ValueError(f"nlcg_direction: unknown variant {variant}")
+    if g0 is not None:
+        g0 = require(g0, "g0")
+        if g0.shape != g1.shape or g0.dtype != g1.dtype:
+            raise ValueError("nlcg_direction: g0 must match g1")
+    elif variant == NLCG_PR and not restart:
+        raise ValueError("nlcg_direction: the PR variant needs g0")
+    if p_new.data_ptr() in (p.data_ptr(), g1.data_ptr()):
+        raise ValueError("nlcg_direction: p_new must not alias p or g1")
+    for t, name in ((gg0, "gg0"), (gg_out, "gg_out")):
+        if t.dtype != torch.float64 or t.numel() != rows or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"nlcg_direction: {name} must be a contiguous float64 device vector of {rows} entries")
+    if gg_out.data_ptr() == gg0.data_ptr():
+        raise ValueError("nlcg_direction: gg_out must not be gg0")
+    need = int(lib.pxa_nlcg_workspace_bytes(rows))
+    if work.dtype != torch.float64 or not work.is_cuda or work.numel() * 8 < need:
+        raise ValueError(f"nlcg_direction: work must be a float64 device tensor of >= {need} bytes")
+    seq, vp_, fp_ = 0, None, None
+    if isinstance(gg_host, HostFlagBuffer):
+        if len(gg_host.values) < rows or len(gg_host.flags) != rows:
+            raise ValueError("nlcg_direction: the HostFlagBuffer must hold rows values and rows flags")
+        seq, vp_, fp_ = gg_host.next_seq(), gg_host.vptr, gg_host.fptr
+    elif gg_host is not None:
+        vp_ = gg_host.data_ptr()
+    check(lib.pxa_nlcg_direction(dtcode(g1), int(variant), int(bool(restart)), rows, n, ptr(g1),
+                                 ptr(g0) if g0 is not None else None, ptr(p), ptr(p_new), gg0.data_ptr(),
+                                 gg_out.data_ptr(), vp_, fp_, seq, work.data_ptr(), stream()), "pxa_nlcg_direction")
+    return seq
+
+
+def ls_armijo(f_trial, f_x, gp, nb, c, r, a, trials, fb):
+    """pxa_ls_armijo: the Armijo test of one backtracking trial on every row.  f_trial, f_x, a: `rows` values of
+    one dtype (a is updated in place: a *= r where f_trial > f_x + a c <g, p>); gp: float64 device, nb partials
+    per row (nb > 0, as nlcg_gp_partials) or one folded value per row (nb == 0); trials: int32 device (rows,),
+    incremented on failing rows; fb: a HostFlagBuffer(1, 1, 1) that receives the number of failing rows
+    (ls_failed(fb, seq) reads it).  Returns the publication's sequence number."""
+    torch = _torch()
+    f_trial, f_x = require(f_trial, "f_trial"), require(f_x, "f_x")
+    if not require(a, "a") is a:
+        raise ValueError("ls_armijo: a is updated in place and must be contiguous")
+    rows = a.numel()
+    if not 1 <= rows <= 65535:
+        raise ValueError(f"ls_armijo: rows must be in [1, 65535], got {rows}")
+    if f_trial.numel() != rows or f_x.numel() != rows or f_trial.dtype != a.dtype or f_x.dtype != a.dtype:
+        raise ValueError("ls_armijo: f_trial, f_x and a must hold one value per row in one dtype")
+    nb = int(nb)
+    if not 0 <= nb <= _CG_BLOCKS:
+        raise ValueError(f"ls_armijo: nb must be in [0, {_CG_BLOCKS}], got {nb}")
+    if gp.dtype != torch.float64 or not gp.is_cuda or not gp.is_contiguous() or gp.numel() < rows * max(nb, 1):
+        raise ValueError("ls_armijo: gp must be a contiguous float64 device tensor of rows * max(nb, 1) entries")
+    if trials.dtype != torch.int32 or not trials.is_cuda or not trials.is_contiguous() or trials.numel() != rows:
+        raise ValueError("ls_armijo: trials must be a contiguous int32 device vector of `rows` entries")
+    if not isinstance(fb, HostFlagBuffer) or len(fb.values) < 1 or len(fb.flags) != 1:
+        raise ValueError("ls_armijo: fb must be a HostFlagBuffer(1, 1, 1)")
+    seq = fb.next_seq()
+    check(lib.pxa_ls_armijo(dtcode(a), rows, ptr(f_trial), ptr(f_x), gp.data_ptr(), nb, float(c), float(r), ptr(a),
+                            trials.data_ptr(), fb.vptr, fb.fptr, seq, stream()), "pxa_ls_armijo")
+    return seq
+
+
+def ls_failed(fb, seq):
+    """Number of rows that failed the Armijo test of publication `seq` (waits for its flag; one 4-byte read)."""
+    fb.wait(seq)
+    return int(fb.values.view(np.uint32)[0])
+
+
 def dense_normal_pfold(A, r, p, p_new, rr, rr_out, fb, seq, s, d, work, pdot):
     """pxa_dense_normal_pdot_pfold: p_new = r + beta p (the CG's previous p update, beta from cg_update_xr's ||r'||^2
     partials at pdot + 64 doubles and `rr`), then Y = s A^T (A p_new) + d p_new and the <p_new, Y> partials into

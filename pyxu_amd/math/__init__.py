@@ -1,9 +1,11 @@
-"""Linear-algebra helpers (reference pyxu.math.linalg.norm :14-22) on device tensors."""
+"""Linear-algebra helpers (reference pyxu.math.linalg.norm :14-22) and the backtracking line search (reference
+pyxu.math.linesearch) on device tensors."""
 import numpy as np
 
 from pyxu_amd import _dev
+from pyxu_amd.math.linesearch import LINESEARCH_DEFAULT_C, LINESEARCH_DEFAULT_R, backtracking_linesearch  # noqa: F401
 
-__all__ = ["norm"]
+__all__ = ["norm", "backtracking_linesearch"]
 
 
 def norm(x, ord=None, axis=None, keepdims=False):

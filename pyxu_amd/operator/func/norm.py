@@ -1,4 +1,6 @@
 """Norm functionals (mirrors reference operator/func/norm.py): L1, L2, SquaredL2, SquaredL1, L21, LInfinity."""
+import types
+
 import numpy as np
 
 import pyxu_amd.abc as pxa
@@ -40,6 +42,21 @@ class L1Norm(_ShiftLossMixin, pxa.ProxFunc):
     @pxrt.enforce_precision(i=("arr", "sigma"))
     def fenchel_prox(self, arr, sigma):
         return _dev.fenchel_prox_l1(arr, sigma, 1.0)
+
+    def moreau_envelope(self, mu):
+        """The Huber function.  Its gradient (x - prox_{mu |.|}(x)) / mu is formed as clip(x, -mu, mu) / mu: the same
+        bits where |x| <= mu (x - 0 is exact), and exactly +-1 beyond, where the generic form cancels (x - (x - mu)
+        carries the rounding of x - mu, magnified by 1 / mu: 20 ulp of x at mu = 0.05).  A line-search solver on a
+        Huber-TV objective follows the float64 trajectory several times closer in float32 with it."""
+        op = super().moreau_envelope(mu)
+
+        @pxrt.enforce_precision(i="arr")
+        def op_grad(_, arr):
+            x = _dev.clip(arr, -_._mu, _._mu)
+            return _dev.div(x, _._mu, out=x)
+
+        op.grad = types.MethodType(op_grad, op)
+        return op
 
 
 class L2Norm(_ShiftLossMixin, pxa.ProxFunc):
