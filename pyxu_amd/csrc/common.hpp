@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/pyxu_amd.h"
 
 namespace pxa {
@@ -58,6 +60,24 @@ int tuning(int key);
 // Elements per 16-byte vector.
 template <typename T>
 constexpr int kVecN = 16 / sizeof(T);
+
+// Run-time stencil radius -> template argument: f(std::integral_constant<int, r>) for the r in LO .. 8 that equals
+// R; any other value takes 8 (the callers reject radii above 8 beforehand).  Instantiates f for LO .. 8 only.
+template <int LO, typename F>
+inline int with_radius(int R, F&& f) {
+  if constexpr (LO < 8) {
+    if (R == LO) return f(std::integral_constant<int, LO>{});
+    return with_radius<LO + 1>(R, f);
+  } else {
+    return f(std::integral_constant<int, 8>{});
+  }
+}
+
+// Run-time flag -> template argument: f(std::true_type) or f(std::false_type).
+template <typename F>
+inline int with_bool(bool b, F&& f) {
+  return b ? f(std::true_type{}) : f(std::false_type{});
+}
 
 // DPP operand of one double (two 32-bit halves through the same lane permutation)
 template <int CTRL>

@@ -37,6 +37,10 @@
 //    C is uniform per march step, so ghost or owned is a choice of base pointer; the ghost-aware forms are
 //    separate instantiations (GhostA / PdsPtrsSlab / GhostC; pds_slab_f32.hip, pds_slab_f64.hip), and the
 //    unsharded launches keep their code.  Same expressions per voxel: the bits of pxa_pds_step.
+// Host side, one path for the five entry points: pds_setup (algorithm, make_geom, tap windows, scalars), step_arrays
+// and the entry's own conditions, then the stages -- pxa_pds_step: stage_a, stage_b, run_c; pxa_pds_slab_primal: its
+// ghost checks, stage_a with a GhostA, stage_b; pxa_pds_step_la: run_d (priming), stage_b, run_d.  pxa_tv_dual_update
+// and pxa_pds_slab_dual are dual_entry (make_geom + run_c) without and with a GhostC.
 // Compulsory HBM traffic per voxel (fp32): PD3O A 24 B + B 24 B + C 28 B = 76 B (80 B);
 // Condat-Vu A 8 B + B 32 B + C 28 B = 68 B (SURVEY: 68 B).
 //
@@ -585,21 +589,18 @@ int run_c(const PdsGeom<T>& g, T sigma, T lam, T rho, T omr, bool pd3o, bool iso
   return pd3o ? launch_c<T, 1, true>(pc, iso, M, cseg, w, z, z_out, st) : launch_c<T, 1, false>(pc, iso, M, cseg, w, z, z_out, st);
 }
 
-// pxa_tv_dual_update: kernel C alone (the "Gradient + prox" kernel of SURVEY §8(d), K4)
+// The geometry every entry point hands to its kernels, validated: sizes, D in {2, 3}, forward-difference taps `diff`
+// = (c0 per axis, c1 per axis).
 template <typename T>
-int dual_entry(int relax, const int64_t* geom, const double* diff, double sigma, double lam, double rho, int h_kind,
-               const void* w, const void* z, void* z_out, hipStream_t st) {
-  PXA_CHECK_ARG(geom && diff && w && z && z_out && z_out != w);
-  PXA_CHECK_ARG(relax == 0 || relax == 1);
-  PXA_CHECK_ARG(h_kind == 0 || h_kind == 1);
-  const int64_t stack = geom[0], n0 = geom[1], n1 = geom[2], n2 = geom[3], D = geom[4];
-  PXA_CHECK_ARG(stack >= 1 && stack <= 65535 && n0 >= 1 && n1 >= 1 && n2 >= 1);
-  PXA_CHECK_ARG(n0 <= 0x7fffffff && n1 <= 0x7fffffff && n2 <= 0x7fffffff && n0 * n1 * n2 <= ((int64_t)1 << 40));
+int make_geom(int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int64_t n2, int64_t D, const double* diff,
+              PdsGeom<T>& g) {
+  PXA_CHECK_ARG(diff != nullptr);
+  PXA_CHECK_ARG(stack >= 1 && stack <= 65535 && y_images >= 1 && stack % y_images == 0);
+  PXA_CHECK_ARG(n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= 0x7fffffff && n1 <= 0x7fffffff && n2 <= 0x7fffffff);
+  PXA_CHECK_ARG(n0 * n1 * n2 <= ((int64_t)1 << 40));
   PXA_CHECK_ARG(D == 2 || D == 3);
-  PXA_CHECK_ARG(D == 3 || n0 == 1);
-  PdsGeom<T> g;
   g.stack = stack;
-  g.y_images = 1;
+  g.y_images = y_images;
   g.n0 = (int)n0;
   g.n1 = (int)n1;
   g.n2 = (int)n2;
@@ -608,17 +609,35 @@ int dual_entry(int relax, const int64_t* geom, const double* diff, double sigma,
     g.c0[a] = (T)diff[a];
     g.c1[a] = (T)diff[3 + a];
   }
-  return run_c<T>(g, (T)sigma, (T)lam, (T)rho, (T)(1.0 - rho), relax == 0, h_kind == 1, w, z, z_out, st);
+  return PXA_OK;
 }
 
-// dense tap window (index t + R) of one axis from (offset, coefficient) lists; returns the radius or -1
-inline int tap_window(int nt, const int32_t* off, const double* coef, double (&k)[2 * kMaxR + 1]) {
-  for (double& v : k) v = 0.0;
-  int R = 0;
-  for (int q = 0; q < nt; ++q) R = abs(off[q]) > R ? abs(off[q]) : R;
-  if (R > kMaxR) return -1;
-  for (int q = 0; q < nt; ++q) k[off[q] + kMaxR] += coef[q];
-  return R;
+// Kernel C alone.  pxa_tv_dual_update (slab == nullptr; the "Gradient + prox" kernel of SURVEY §8(d), K4): a whole
+// stack of volumes, or of images with D = 2.  pxa_pds_slab_dual: one rank's slab of a volume, w at plane n0 from the
+// next slab (slab->w_hi as (stack, dhi, n1, n2); null: the volume's edge).
+template <typename T>
+int dual_entry(int relax, const int64_t* geom, const double* diff, double sigma, double lam, double rho, int h_kind,
+               const void* w, const void* z, void* z_out, hipStream_t st, const GhostC<T>* slab = nullptr) {
+  PXA_CHECK_ARG(geom && w && z && z_out && z_out != w);
+  PXA_CHECK_ARG(relax == 0 || relax == 1);
+  PXA_CHECK_ARG(h_kind == 0 || h_kind == 1);
+  PdsGeom<T> g;
+  if (const int e = make_geom<T>(geom[0], 1, geom[1], geom[2], geom[3], geom[4], diff, g)) return e;
+  GhostC<T> gh{nullptr, 0};
+  if (!slab) {
+    PXA_CHECK_ARG(g.D == 3 || g.n0 == 1);
+  } else {
+    PXA_CHECK_ARG(g.D == 3 || g.n0 > 1);  // volumes only: an image has no axis-0 neighbour
+    PXA_CHECK_ARG(slab->dhi >= 0 && slab->dhi <= 0x7fffffff);
+    if (slab->w_hi != nullptr) {
+      PXA_CHECK_ARG(g.D == 3);         // axis 0 not differentiated: no ghost is read
+      PXA_CHECK_ARG(slab->dhi >= 1);   // kernel C reads one plane ahead
+      PXA_CHECK_ARG(slab->w_hi != z_out);
+      gh = *slab;
+    }
+  }
+  return run_c<T>(g, (T)sigma, (T)lam, (T)rho, (T)(1.0 - rho), relax == 0, h_kind == 1, w, z, z_out, st,
+                  slab ? &gh : nullptr);
 }
 
 // Measurement hook (PXA_TUNE_PDS_EVENTS > 0, bench.py's c3 record): HIP events recorded on the launch stream
@@ -643,13 +662,13 @@ static void pds_event(int k, hipStream_t st) {
   if (k == 3) ++E.used;
 }
 
-// Validated geometry, taps and scalars shared by the three-launch and the look-ahead step.
+// Validated algorithm, geometry, taps and scalars shared by the three-launch, the slab and the look-ahead step.
 template <typename T>
 struct PdsSetup {
   PdsGeom<T> g;
-  double kw[3][2 * kMaxR + 1];
+  TapWindow kw[3];
   int R0, R;  // axis-0 radius (0: axis 0 not blurred), in-plane radius
-  bool id0;
+  bool pd3o, id0;
   T tau, sigma, rho, lam, pw, omr;
   int64_t M;
   int prox;
@@ -657,14 +676,11 @@ struct PdsSetup {
 };
 
 template <typename T>
-int pds_setup(const int64_t* geom, const int32_t* ntaps, const int32_t* offs, const double* coefs, const double* diff,
-              const double* scal, int prox, int h_kind, PdsSetup<T>& S) {
-  PXA_CHECK_ARG(geom && ntaps && offs && coefs && diff && scal);
-  const int64_t stack = geom[0], y_images = geom[1], n0 = geom[2], n1 = geom[3], n2 = geom[4], D = geom[5];
-  PXA_CHECK_ARG(stack >= 1 && y_images >= 1 && stack % y_images == 0);
-  PXA_CHECK_ARG(n0 >= 1 && n1 >= 1 && n2 >= 1 && n0 <= 0x7fffffff && n1 <= 0x7fffffff && n2 <= 0x7fffffff);
-  PXA_CHECK_ARG(D == 2 || D == 3);
-  PXA_CHECK_ARG(stack <= 65535 && n0 * n1 * n2 <= ((int64_t)1 << 40));
+int pds_setup(int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs, const double* coefs,
+              const double* diff, const double* scal, int prox, int h_kind, PdsSetup<T>& S) {
+  PXA_CHECK_ARG(algo == 0 || algo == 1);
+  PXA_CHECK_ARG(geom && ntaps && offs && coefs && scal);
+  if (const int e = make_geom<T>(geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], diff, S.g)) return e;
   PXA_CHECK_ARG(prox >= 0 && prox <= 2 && (h_kind == 0 || h_kind == 1));
   for (int a = 0; a < 3; ++a) PXA_CHECK_ARG(ntaps[a] >= 1 && ntaps[a] <= 2 * kMaxR + 1);
   int Ra[3];
@@ -677,26 +693,26 @@ int pds_setup(const int64_t* geom, const int32_t* ntaps, const int32_t* offs, co
   S.R0 = S.id0 ? 0 : (Ra[0] > 0 ? Ra[0] : 1);
   S.R = Ra[1] > Ra[2] ? Ra[1] : Ra[2];
   if (S.R < 1) S.R = 1;
-  PdsGeom<T>& g = S.g;
-  g.stack = stack;
-  g.y_images = y_images;
-  g.n0 = (int)n0;
-  g.n1 = (int)n1;
-  g.n2 = (int)n2;
-  g.D = (int)D;
-  for (int a = 0; a < 3; ++a) {
-    g.c0[a] = (T)diff[a];
-    g.c1[a] = (T)diff[3 + a];
-  }
+  S.pd3o = algo == 0;
   S.tau = (T)scal[0];
   S.sigma = (T)scal[1];
   S.rho = (T)scal[2];
   S.lam = (T)scal[3];
   S.pw = (T)scal[4];
   S.omr = (T)(1.0 - scal[2]);
-  S.M = n1 * n2;
+  S.M = (int64_t)S.g.n1 * S.g.n2;
   S.prox = prox;
   S.iso = h_kind == 1;
+  return PXA_OK;
+}
+
+// The array arguments every step needs: z, S^T y, x_out and w; PD3O its u pair; work_q when axis 0 is blurred.
+template <typename T>
+int step_arrays(const PdsSetup<T>& S, const void* u, const void* z, const void* hty, const void* x_out,
+                const void* u_out, const void* work_q, const void* work_w) {
+  PXA_CHECK_ARG(z && hty && x_out && work_w);
+  PXA_CHECK_ARG(!S.pd3o || (u && u_out));
+  PXA_CHECK_ARG(S.id0 || work_q != nullptr);
   return PXA_OK;
 }
 
@@ -705,8 +721,7 @@ template <typename T>
 PdsA<T> make_a(const PdsSetup<T>& S, int& nseg) {
   PdsA<T> pa;
   pa.g = S.g;
-  for (int t = 0; t < 2 * kMaxR0 + 1; ++t) pa.k0[t] = T(0);
-  for (int t = -S.R0; t <= S.R0; ++t) pa.k0[t + S.R0] = (T)S.kw[0][t + kMaxR];
+  tap_dense(S.kw[0], S.R0, pa.k0);
   pa.tau = S.tau;
   pa.pw = S.pw;
   pa.prox = S.prox;
@@ -725,12 +740,32 @@ PdsA<T> make_a(const PdsSetup<T>& S, int& nseg) {
   return pa;
 }
 
+template <typename T>
+inline bool aligned_pair(const void* p) {
+  return (uintptr_t)p % (2 * sizeof(T)) == 0;
+}
+
+// kernel A on src = u (PD3O: v = prox_g(u - tau K^T z) -> x_out) or x (Condat-Vu), Q = G0 v -> work_q; it runs
+// unless Condat-Vu has nothing to march (axis 0 not blurred).  *q_src: kernel B's input plane stack.  gh: the slab
+// form's ghost planes; pairs: the caller's ghost buffers allow kernel A's two-position path.
+template <typename T>
+int stage_a(const PdsSetup<T>& S, int nseg, const void* src, const void* z, void* x_out, void* work_q,
+            const void** q_src, hipStream_t st, const GhostA<T>* gh = nullptr, bool pairs = true) {
+  *q_src = !S.id0 ? work_q : S.pd3o ? x_out : src;
+  if (!S.pd3o && S.id0) return PXA_OK;
+  const PdsA<T> pa = make_a(S, nseg);
+  const bool np2 = pairs && (S.g.n2 % 2 == 0) && aligned_pair<T>(src) && aligned_pair<T>(z) &&
+                   aligned_pair<T>(x_out) && (S.id0 || aligned_pair<T>(work_q));
+  void* q = S.id0 ? x_out : work_q;  // R0 == 0 never writes q
+  return gh ? run_a_slab(pa, *gh, S.pd3o, S.R0, np2 ? 2 : 1, S.M, nseg, src, z, x_out, q, st)
+            : run_a(pa, S.pd3o, S.R0, np2 ? 2 : 1, S.M, nseg, src, z, x_out, q, st);
+}
+
 // kernel B: mode 0 PD3O, 1 Condat-Vu (K^T z from z), 2 Condat-Vu (K^T z given in `z`)
 template <typename T>
 int stage_b(const PdsSetup<T>& S, int mode, const void* q_src, const void* xin, const void* u, const void* z,
             const void* hty, void* w, void* out, hipStream_t st, const PdsPtrsSlab* slab = nullptr) {
   constexpr int V = kVecN<T>;
-  const int R = S.R;
   PdsB<T> pb;
   pb.g = S.g;
   pb.tiles1 = (int)((S.g.n1 + TY - 1) / TY);
@@ -738,22 +773,10 @@ int stage_b(const PdsSetup<T>& S, int mode, const void* q_src, const void* xin, 
   const int64_t ntiles = S.g.stack * S.g.n0 * pb.tiles1 * pb.tiles2;
   PXA_CHECK_ARG(ntiles <= 0x7fffffff);
   pb.ntiles = (unsigned)ntiles;
-  for (int j = 0; j < 2 * kMaxR + 1; ++j) pb.k1[j] = pb.k2[j] = T(0);
-  for (int t = -R; t <= R; ++t) {
-    pb.k1[t + R] = (T)S.kw[1][t + kMaxR];
-    pb.k2[t + R] = (T)S.kw[2][t + kMaxR];
-  }
-  for (int j = 0; j < kMaxG; ++j) pb.g1[j] = pb.g2[j] = T(0);
-  for (int d = -2 * R; d <= 2 * R; ++d) {
-    double s1 = 0.0, s2 = 0.0;
-    for (int t = -R; t <= R; ++t) {
-      if (t + d < -R || t + d > R) continue;
-      s1 += S.kw[1][t + kMaxR] * S.kw[1][t + d + kMaxR];
-      s2 += S.kw[2][t + kMaxR] * S.kw[2][t + d + kMaxR];
-    }
-    pb.g1[d + 2 * R] = (T)s1;
-    pb.g2[d + 2 * R] = (T)s2;
-  }
+  tap_dense(S.kw[1], S.R, pb.k1);
+  tap_dense(S.kw[2], S.R, pb.k2);
+  tap_autocorr(S.kw[1], S.R, pb.g1);
+  tap_autocorr(S.kw[2], S.R, pb.g2);
   pb.tau = S.tau;
   pb.rho = S.rho;
   pb.omr = S.omr;
@@ -765,88 +788,36 @@ int stage_b(const PdsSetup<T>& S, int mode, const void* q_src, const void* xin, 
   if (slab) {  // mode 1 on a slab: the z_0 ghost plane
     pb.vec_ok = pb.vec_ok && aligned16(slab->z_lo);
     PdsPtrsSlab PS{P, slab->z_lo, slab->z_dlo};
-    return run_b_slab(pb, R, PS, st);
+    return run_b_slab(pb, S.R, PS, st);
   }
-  return run_b(pb, mode, R, P, st);
+  return run_b(pb, mode, S.R, P, st);
 }
 
+// pxa_pds_step: setup, checks, kernels A, B, C
 template <typename T>
 int pds_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs, const double* coefs,
               const double* diff, const double* scal, int prox, int h_kind, const void* x, const void* u,
               const void* z, const void* hty, void* x_out, void* u_out, void* z_out, void* work_q, void* work_w,
               int nseg, hipStream_t st) {
-  PXA_CHECK_ARG(algo == 0 || algo == 1);
   PdsSetup<T> S;
-  if (const int e = pds_setup<T>(geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
-  const bool pd3o = algo == 0;
-  PXA_CHECK_ARG(z && hty && z_out && work_w && x_out && (pd3o ? (u && u_out) : (x != nullptr)));
-  PXA_CHECK_ARG(pd3o || x_out != x);  // kernel B reads x windows (halos) while writing x_out
-  if (!S.id0) PXA_CHECK_ARG(work_q != nullptr);
-  const PdsGeom<T>& g = S.g;
-  const int64_t M = S.M;
+  if (const int e = pds_setup<T>(algo, geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
+  if (const int e = step_arrays(S, u, z, hty, x_out, u_out, work_q, work_w)) return e;
+  PXA_CHECK_ARG(z_out != nullptr);
+  PXA_CHECK_ARG(S.pd3o || (x && x_out != x));  // kernel B reads x windows (halos) while writing x_out
+  const bool pd3o = S.pd3o;
 
   const bool evs = tuning(PXA_TUNE_PDS_EVENTS) > 0;
   if (evs) pds_event(0, st);
-  // ---- kernel A
-  const void* q_src = pd3o ? (const void*)x_out : x;  // kernel B's input plane stack
-  if (pd3o || !S.id0) {
-    const PdsA<T> pa = make_a(S, nseg);
-    const void* src = pd3o ? u : x;
-    const bool np2 = (g.n2 % 2 == 0) && ((uintptr_t)src % (2 * sizeof(T)) == 0) &&
-                     ((uintptr_t)z % (2 * sizeof(T)) == 0) && ((uintptr_t)x_out % (2 * sizeof(T)) == 0) &&
-                     (S.id0 || (uintptr_t)work_q % (2 * sizeof(T)) == 0);
-    void* q = S.id0 ? x_out : work_q;  // R0 == 0 never writes q
-    const int e = run_a(pa, pd3o, S.R0, np2 ? 2 : 1, M, nseg, src, z, x_out, q, st);
-    if (e) return e;
-    if (!S.id0) q_src = work_q;
-  }
+  const void* q_src;
+  if (const int e = stage_a<T>(S, nseg, pd3o ? u : x, z, x_out, work_q, &q_src, st)) return e;
   if (evs) pds_event(1, st);
-
-  // ---- kernel B
-  {
-    const int e = stage_b(S, pd3o ? 0 : 1, q_src, pd3o ? (const void*)x_out : x, u, z, hty, work_w,
-                          pd3o ? u_out : x_out, st);
-    if (e) return e;
-  }
+  if (const int e = stage_b(S, pd3o ? 0 : 1, q_src, pd3o ? (const void*)x_out : x, u, z, hty, work_w,
+                            pd3o ? u_out : x_out, st))
+    return e;
   if (evs) pds_event(2, st);
-
-  // ---- kernel C
-  if (const int e = run_c<T>(g, S.sigma, S.lam, S.rho, S.omr, pd3o, S.iso, work_w, z, z_out, st)) return e;
+  if (const int e = run_c<T>(S.g, S.sigma, S.lam, S.rho, S.omr, pd3o, S.iso, work_w, z, z_out, st)) return e;
   if (evs) pds_event(3, st);
   return PXA_OK;
-}
-
-// pxa_pds_slab_dual: kernel C on one rank's slab, w at plane nl from the next slab (w_hi; null: the volume's edge)
-template <typename T>
-int dual_slab_entry(int relax, const int64_t* geom, const double* diff, double sigma, double lam, double rho,
-                    int h_kind, const void* w, const void* w_hi, int64_t w_hi_depth, const void* z, void* z_out,
-                    hipStream_t st) {
-  PXA_CHECK_ARG(geom && diff && w && z && z_out && z_out != w);
-  PXA_CHECK_ARG(relax == 0 || relax == 1);
-  PXA_CHECK_ARG(h_kind == 0 || h_kind == 1);
-  const int64_t stack = geom[0], n0 = geom[1], n1 = geom[2], n2 = geom[3], D = geom[4];
-  PXA_CHECK_ARG(stack >= 1 && stack <= 65535 && n0 >= 1 && n1 >= 1 && n2 >= 1);
-  PXA_CHECK_ARG(n0 <= 0x7fffffff && n1 <= 0x7fffffff && n2 <= 0x7fffffff && n0 * n1 * n2 <= ((int64_t)1 << 40));
-  PXA_CHECK_ARG(D == 3 || (D == 2 && n0 > 1));  // volumes only: an image has no axis-0 neighbour
-  PXA_CHECK_ARG(w_hi_depth >= 0 && w_hi_depth <= 0x7fffffff);
-  if (w_hi != nullptr) {
-    PXA_CHECK_ARG(D == 3);             // axis 0 not differentiated: no ghost is read
-    PXA_CHECK_ARG(w_hi_depth >= 1);    // kernel C reads one plane ahead
-    PXA_CHECK_ARG(w_hi != z_out);
-  }
-  PdsGeom<T> g;
-  g.stack = stack;
-  g.y_images = 1;
-  g.n0 = (int)n0;
-  g.n1 = (int)n1;
-  g.n2 = (int)n2;
-  g.D = (int)D;
-  for (int a = 0; a < 3; ++a) {
-    g.c0[a] = (T)diff[a];
-    g.c1[a] = (T)diff[3 + a];
-  }
-  const GhostC<T> gh{(const T*)w_hi, w_hi != nullptr ? w_hi_depth : 0};
-  return run_c<T>(g, (T)sigma, (T)lam, (T)rho, (T)(1.0 - rho), relax == 0, h_kind == 1, w, z, z_out, st, &gh);
 }
 
 // pxa_pds_slab_primal: kernels A and B of pds_entry on one rank's slab.  ghost = {src_lo, src_hi, z_lo, z_hi}
@@ -860,13 +831,11 @@ int pds_slab_entry(int algo, const int64_t* geom, const int32_t* ntaps, const in
                    const void* z, const void* hty, void* x_out, void* u_out, void* work_q, void* work_w,
                    const int64_t* ghost, const void* src_lo, const void* src_hi, const void* z_lo, const void* z_hi,
                    int nseg, hipStream_t st) {
-  PXA_CHECK_ARG(algo == 0 || algo == 1);
   PdsSetup<T> S;
-  if (const int e = pds_setup<T>(geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
-  const bool pd3o = algo == 0;
-  PXA_CHECK_ARG(z && hty && work_w && x_out && (pd3o ? (u && u_out) : (x != nullptr)));
-  PXA_CHECK_ARG(pd3o || x_out != x);
-  if (!S.id0) PXA_CHECK_ARG(work_q != nullptr);
+  if (const int e = pds_setup<T>(algo, geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
+  if (const int e = step_arrays(S, u, z, hty, x_out, u_out, work_q, work_w)) return e;
+  PXA_CHECK_ARG(S.pd3o || (x && x_out != x));
+  const bool pd3o = S.pd3o;
   const PdsGeom<T>& g = S.g;
   PXA_CHECK_ARG(g.n0 > 1 || g.D == 3);  // volumes only (n0 = 1 / D = 2 images have no axis-0 neighbour)
   const bool any = src_lo || src_hi || z_lo || z_hi;
@@ -887,33 +856,23 @@ int pds_slab_entry(int algo, const int64_t* geom, const int32_t* ntaps, const in
   if (lo) PXA_CHECK_ARG(d[2] >= (pd3o ? R2 + 1 : 1) && (!need_src || d[0] >= R2));
   if (hi) PXA_CHECK_ARG((!need_src || d[1] >= R2) && (!need_zhi || d[3] >= R2));
   const void* ghosts[4] = {src_lo, src_hi, z_lo, z_hi};
-  for (const void* gp : ghosts)
+  bool pairs = true;
+  for (const void* gp : ghosts) {
     if (gp) PXA_CHECK_ARG(gp != x_out && gp != u_out && gp != work_q && gp != work_w);
-  const int64_t M = S.M;
-
-  // ---- kernel A
-  const void* q_src = pd3o ? (const void*)x_out : x;
-  if (pd3o || !S.id0) {
-    const PdsA<T> pa = make_a(S, nseg);
-    const void* src = pd3o ? u : x;
-    auto a2 = [](const void* p) { return (uintptr_t)p % (2 * sizeof(T)) == 0; };
-    const bool np2 = (g.n2 % 2 == 0) && a2(src) && a2(z) && a2(x_out) && (S.id0 || a2(work_q)) && a2(src_lo) &&
-                     a2(src_hi) && a2(z_lo) && a2(z_hi);
-    GhostA<T> gh;
-    gh.src_lo = need_src && lo ? (const T*)src_lo : nullptr;
-    gh.src_hi = need_src && hi ? (const T*)src_hi : nullptr;
-    gh.z_lo = pd3o && lo ? (const T*)z_lo : nullptr;
-    gh.z_hi = need_zhi && hi ? (const T*)z_hi : nullptr;
-    gh.src_dlo = (int)d[0];
-    gh.src_dhi = (int)d[1];
-    gh.z_dlo = (int)d[2];
-    gh.z_dhi = (int)d[3];
-    void* q = S.id0 ? x_out : work_q;  // R0 == 0 never writes q
-    const int e = run_a_slab(pa, gh, pd3o, S.R0, np2 ? 2 : 1, M, nseg, src, z, x_out, q, st);
-    if (e) return e;
-    if (!S.id0) q_src = work_q;
+    pairs = pairs && aligned_pair<T>(gp);
   }
-  // ---- kernel B
+
+  GhostA<T> gh;
+  gh.src_lo = need_src && lo ? (const T*)src_lo : nullptr;
+  gh.src_hi = need_src && hi ? (const T*)src_hi : nullptr;
+  gh.z_lo = pd3o && lo ? (const T*)z_lo : nullptr;
+  gh.z_hi = need_zhi && hi ? (const T*)z_hi : nullptr;
+  gh.src_dlo = (int)d[0];
+  gh.src_dhi = (int)d[1];
+  gh.z_dlo = (int)d[2];
+  gh.z_dhi = (int)d[3];
+  const void* q_src;
+  if (const int e = stage_a<T>(S, nseg, pd3o ? u : x, z, x_out, work_q, &q_src, st, &gh, pairs)) return e;
   if (pd3o) return stage_b(S, 0, q_src, x_out, u, z, hty, work_w, u_out, st);
   const PdsPtrsSlab zl{{}, lo ? z_lo : nullptr, lo ? d[2] : 0};
   return stage_b(S, 1, q_src, x, u, z, hty, work_w, x_out, st, &zl);
@@ -928,13 +887,12 @@ int pds_la_entry(int algo, const int64_t* geom, const int32_t* ntaps, const int3
                  const double* diff, const double* scal, int prox, int h_kind, int primed, void* x, const void* u,
                  const void* z, const void* hty, void* x_out, void* u_out, void* z_out, void* work_q, void* work_kt,
                  void* work_w, int nseg, hipStream_t st) {
-  PXA_CHECK_ARG(algo == 0 || algo == 1);
   PdsSetup<T> S;
-  if (const int e = pds_setup<T>(geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
-  const bool pd3o = algo == 0;
-  PXA_CHECK_ARG(x && z && hty && z_out && work_w && x_out && x_out != x && z_out != z);
-  PXA_CHECK_ARG(pd3o ? (u && u_out) : (work_kt != nullptr));
-  if (!S.id0) PXA_CHECK_ARG(work_q != nullptr);
+  if (const int e = pds_setup<T>(algo, geom, ntaps, offs, coefs, diff, scal, prox, h_kind, S)) return e;
+  if (const int e = step_arrays(S, u, z, hty, x_out, u_out, work_q, work_w)) return e;
+  PXA_CHECK_ARG(x && x_out != x && z_out && z_out != z);
+  PXA_CHECK_ARG(S.pd3o || work_kt != nullptr);
+  const bool pd3o = S.pd3o;
   const int64_t M = S.M;
   PdsD<T> pd;
   pd.a = make_a(S, nseg);
@@ -1023,9 +981,8 @@ int pxa_pds_slab_primal(int dtype, int algo, const int64_t* geom, const int32_t*
 int pxa_pds_slab_dual(int dtype, int relax, const int64_t* geom, const double* diff, double sigma, double lam,
                       double rho, int h_kind, const void* w, const void* w_hi, int64_t w_hi_depth, const void* z,
                       void* z_out, void* stream) {
-  PXA_DISPATCH(dtype, T,
-               return dual_slab_entry<T>(relax, geom, diff, sigma, lam, rho, h_kind, w, w_hi, w_hi_depth, z, z_out,
-                                         as_stream(stream)));
+  PXA_DISPATCH(dtype, T, const GhostC<T> gh{(const T*)w_hi, w_hi_depth};
+               return dual_entry<T>(relax, geom, diff, sigma, lam, rho, h_kind, w, z, z_out, as_stream(stream), &gh));
 }
 
 int pxa_pds_step_la(int dtype, int algo, const int64_t* geom, const int32_t* ntaps, const int32_t* offs,

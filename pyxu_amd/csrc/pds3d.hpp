@@ -603,29 +603,22 @@ int launch_a(const PdsA<T>& pa, int np, int64_t M, int nseg, const void* src, co
              hipStream_t st, GH gh = GH()) {
   const int64_t blocks = (M + (int64_t)kAThreads * np - 1) / ((int64_t)kAThreads * np);
   dim3 grid((unsigned)blocks, (unsigned)nseg, (unsigned)pa.g.stack);
-  if (np == 2)
-    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 2, PD3O, GH>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
-                       (const T*)z, (T*)xo, (T*)q, gh);
-  else
-    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, 1, PD3O, GH>), grid, dim3(kAThreads), 0, st, pa, (const T*)src,
-                       (const T*)z, (T*)xo, (T*)q, gh);
-  return last_launch_status();
+  return with_bool(np == 2, [&](auto two) {
+    hipLaunchKernelGGL((pds_axis0_kernel<T, R0, decltype(two)::value ? 2 : 1, PD3O, GH>), grid, dim3(kAThreads), 0, st,
+                       pa, (const T*)src, (const T*)z, (T*)xo, (T*)q, gh);
+    return last_launch_status();
+  });
 }
 
-template <typename T, bool PD3O, typename GH = NoGhost>
-int dispatch_a(int R0, const PdsA<T>& pa, int np, int64_t M, int nseg, const void* src, const void* z, void* xo,
-               void* q, hipStream_t st, GH gh = GH()) {
-  switch (R0) {
-    case 0: return launch_a<T, 0, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 1: return launch_a<T, 1, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 2: return launch_a<T, 2, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 3: return launch_a<T, 3, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 4: return launch_a<T, 4, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 5: return launch_a<T, 5, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 6: return launch_a<T, 6, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    case 7: return launch_a<T, 7, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-    default: return launch_a<T, 8, PD3O, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
-  }
+// kernel A of axis-0 radius R0 (0 .. 8), PD3O or Condat-Vu, with or without ghost planes
+template <typename T, typename GH = NoGhost>
+int dispatch_a(bool pd3o, int R0, const PdsA<T>& pa, int np, int64_t M, int nseg, const void* src, const void* z,
+               void* xo, void* q, hipStream_t st, GH gh = GH()) {
+  return with_bool(pd3o, [&](auto p) {
+    return with_radius<0>(R0, [&](auto r) {
+      return launch_a<T, decltype(r)::value, decltype(p)::value, GH>(pa, np, M, nseg, src, z, xo, q, st, gh);
+    });
+  });
 }
 
 template <typename T, int R, int MODE, typename PP = PdsPtrs>
@@ -644,16 +637,7 @@ int launch_b(const PdsB<T>& pb, const PP& P, hipStream_t st) {
 
 template <typename T, int MODE, typename PP = PdsPtrs>
 int dispatch_b(int R, const PdsB<T>& pb, const PP& P, hipStream_t st) {
-  switch (R) {
-    case 1: return launch_b<T, 1, MODE, PP>(pb, P, st);
-    case 2: return launch_b<T, 2, MODE, PP>(pb, P, st);
-    case 3: return launch_b<T, 3, MODE, PP>(pb, P, st);
-    case 4: return launch_b<T, 4, MODE, PP>(pb, P, st);
-    case 5: return launch_b<T, 5, MODE, PP>(pb, P, st);
-    case 6: return launch_b<T, 6, MODE, PP>(pb, P, st);
-    case 7: return launch_b<T, 7, MODE, PP>(pb, P, st);
-    default: return launch_b<T, 8, MODE, PP>(pb, P, st);
-  }
+  return with_radius<1>(R, [&](auto r) { return launch_b<T, decltype(r)::value, MODE, PP>(pb, P, st); });
 }
 
 int run_a(const PdsA<float>& pa, bool pd3o, int R0, int np, int64_t M, int nseg, const void* src, const void* z,

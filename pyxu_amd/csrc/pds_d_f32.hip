@@ -4,13 +4,7 @@
 namespace pxa {
 namespace pds {
 
-PXA_PDS_RUN_D(float) {
-#define PXA_D(P, I, U) dispatch_d<float, P, I, U>(R0, pd, M, nseg, w, z, src, zo, ao, q, st)
-  if (!dual) return pd3o ? PXA_D(true, false, false) : PXA_D(false, false, false);
-  if (pd3o) return iso ? PXA_D(true, true, true) : PXA_D(true, false, true);
-  return iso ? PXA_D(false, true, true) : PXA_D(false, false, true);
-#undef PXA_D
-}
+PXA_PDS_RUN_D(float) { return dispatch_d<float>(pd, pd3o, iso, dual, R0, M, nseg, w, z, src, zo, ao, q, st); }
 
 }  // namespace pds
 }  // namespace pxa

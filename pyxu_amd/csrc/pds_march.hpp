@@ -301,24 +301,22 @@ int launch_d(const PdsD<T>& pd, int64_t M, int nseg, const void* w, const void* 
   return last_launch_status();
 }
 
-template <typename T, bool PD3O, bool ISO, bool DUAL>
-int dispatch_d(int R0, const PdsD<T>& pd, int64_t M, int nseg, const void* w, const void* z, const void* src,
-               void* zo, void* ao, void* q, hipStream_t st) {
-  switch (R0) {
-    case 0: return launch_d<T, 0, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 1: return launch_d<T, 1, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 2: return launch_d<T, 2, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 3: return launch_d<T, 3, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 4: return launch_d<T, 4, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 5: return launch_d<T, 5, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 6: return launch_d<T, 6, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    case 7: return launch_d<T, 7, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-    default: return launch_d<T, 8, PD3O, ISO, DUAL>(pd, M, nseg, w, z, src, zo, ao, q, st);
-  }
+// kernel D of axis-0 radius R0 (0 .. 8); dual = false is the priming march (ISO irrelevant: one instantiation)
+template <typename T>
+int dispatch_d(const PdsD<T>& pd, bool pd3o, bool iso, bool dual, int R0, int64_t M, int nseg, const void* w,
+               const void* z, const void* src, void* zo, void* ao, void* q, hipStream_t st) {
+  auto go = [&](auto p, auto i, auto u) {
+    return with_radius<0>(R0, [&](auto r) {
+      return launch_d<T, decltype(r)::value, decltype(p)::value, decltype(i)::value, decltype(u)::value>(
+          pd, M, nseg, w, z, src, zo, ao, q, st);
+    });
+  };
+  if (!dual) return with_bool(pd3o, [&](auto p) { return go(p, std::false_type{}, std::false_type{}); });
+  return with_bool(pd3o, [&](auto p) { return with_bool(iso, [&](auto i) { return go(p, i, std::true_type{}); }); });
 }
 
-// run_d: dual = false is the priming march (ISO irrelevant)
-#define PXA_PDS_RUN_D(T)                                                                                 \
+// run_d: instantiated per dtype in pds_d_f32.hip / pds_d_f64.hip
+#define PXA_PDS_RUN_D(T)                                                                                \
   int run_d(const PdsD<T>& pd, bool pd3o, bool iso, bool dual, int R0, int64_t M, int nseg, const void* w, \
             const void* z, const void* src, void* zo, void* ao, void* q, hipStream_t st)
 PXA_PDS_RUN_D(float);

@@ -6,8 +6,7 @@ namespace pds {
 
 int run_a_slab(const PdsA<float>& pa, const GhostA<float>& gh, bool pd3o, int R0, int np, int64_t M, int nseg,
                const void* src, const void* z, void* xo, void* q, hipStream_t st) {
-  return pd3o ? dispatch_a<float, true, GhostA<float>>(R0, pa, np, M, nseg, src, z, xo, q, st, gh)
-              : dispatch_a<float, false, GhostA<float>>(R0, pa, np, M, nseg, src, z, xo, q, st, gh);
+  return dispatch_a<float>(pd3o, R0, pa, np, M, nseg, src, z, xo, q, st, gh);
 }
 
 int run_b_slab(const PdsB<float>& pb, int R, const PdsPtrsSlab& P, hipStream_t st) {

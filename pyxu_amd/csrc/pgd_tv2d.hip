@@ -981,10 +981,12 @@ int pgd_params(int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0,
   PXA_CHECK_ARG(n0 <= 0x7fffffff && n1 <= 0x7fffffff);
   PXA_CHECK_ARG(prox >= 0 && prox <= 2);
   PXA_CHECK_ARG(nt0 >= 1 && nt1 >= 1 && off0 && off1 && coef0 && coef1);
-  R = 1;  // TV needs a 1-pixel halo even for a 1-tap blur
-  for (int q = 0; q < nt0; ++q) R = abs(off0[q]) > R ? abs(off0[q]) : R;
-  for (int q = 0; q < nt1; ++q) R = abs(off1[q]) > R ? abs(off1[q]) : R;
-  if (R > kMaxR) return PXA_ERR_UNSUPPORTED;
+  // H taps as dense windows in double (code-generation order folded per offset)
+  TapWindow k0, k1;
+  const int r0 = tap_window(nt0, off0, coef0, k0), r1 = tap_window(nt1, off1, coef1, k1);
+  if (r0 < 0 || r1 < 0) return PXA_ERR_UNSUPPORTED;
+  R = r0 > r1 ? r0 : r1;
+  if (R < 1) R = 1;  // TV needs a 1-pixel halo even for a 1-tap blur
   p = PgdParams<T>{};
   p.stack = stack;
   p.y_images = y_images;
@@ -995,25 +997,14 @@ int pgd_params(int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0,
   const int64_t ntiles = stack * (int64_t)p.tiles0 * p.tiles1;
   PXA_CHECK_ARG(ntiles <= 0x7fffffff);
   p.ntiles = (unsigned)ntiles;
-  // H taps as a dense window in double (code-generation order folded per offset), then G = k (*) k
-  double k0[2 * kMaxR + 1] = {0}, k1[2 * kMaxR + 1] = {0};
-  for (int q = 0; q < nt0; ++q) k0[off0[q] + R] += coef0[q];
-  for (int q = 0; q < nt1; ++q) k1[off1[q] + R] += coef1[q];
-  for (int j = 0; j < 2 * kMaxR + 1; ++j) {
-    p.k0[j] = (T)k0[j];
-    p.k1[j] = (T)k1[j];
-  }
-  for (int d = -2 * R; d <= 2 * R; ++d) {
-    double s0 = 0.0, s1 = 0.0;
-    for (int t = -R; t <= R; ++t) {
-      if (t + d < -R || t + d > R) continue;
-      s0 += k0[t + R] * k0[t + d + R];
-      s1 += k1[t + R] * k1[t + d + R];
-    }
-    p.g0[d + 2 * R] = (T)s0;
-    p.g1[d + 2 * R] = (T)s1;
-  }
-  for (int j = 4 * R + 1; j < kMaxG; ++j) p.g0[j] = p.g1[j] = T(0);
+  // rows of the RelError statistics = rows of the solver state: y_images images each (batch-as-axis); the
+  // slots of one image, hence of one row, are contiguous
+  p.fold_rows = stack / y_images;
+  p.fold_per_row = ntiles * (kThreads / 64) / p.fold_rows;
+  tap_dense(k0, R, p.k0);
+  tap_dense(k1, R, p.k1);
+  tap_autocorr(k0, R, p.g0);  // G = k (*) k
+  tap_autocorr(k1, R, p.g1);
   p.g0a = (T)(-1.0 / h0);
   p.g0b = (T)(1.0 / h0);
   p.g1a = (T)(-1.0 / h1);
@@ -1047,10 +1038,6 @@ int pgd_run(PgdParams<T> p, int R, double a, double tau, double prox_w, const vo
   p.fold_flags = (unsigned*)rel_flags;
   p.fold_seq = (unsigned)seq;
   p.counter = counter;
-  // rows of the RelError statistics = rows of the solver state: y_images images each (batch-as-axis); the
-  // slots of one image, hence of one row, are contiguous
-  p.fold_rows = p.stack / p.y_images;
-  p.fold_per_row = (int64_t)p.ntiles * (kThreads / 64) / p.fold_rows;
   p.win_part = win_part;
   PXA_CHECK_ARG(!win_part || (partials != nullptr && rel_values == nullptr));
   PXA_CHECK_ARG(pub_src == nullptr || (pub_vals != nullptr && pub_flags != nullptr && pub_src != partials));
@@ -1058,18 +1045,9 @@ int pgd_run(PgdParams<T> p, int R, double a, double tau, double prox_w, const vo
   p.pub_vals = pub_vals;
   p.pub_flags = (unsigned*)pub_flags;
   p.pub_seq = (unsigned)pub_seq;
-  int st;
-  switch (R) {
-    case 1: st = launch_pgd<T, 1>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 2: st = launch_pgd<T, 2>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 3: st = launch_pgd<T, 3>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 4: st = launch_pgd<T, 4>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 5: st = launch_pgd<T, 5>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 6: st = launch_pgd<T, 6>(p, x, x_prev, hty, x_new, partials, s); break;
-    case 7: st = launch_pgd<T, 7>(p, x, x_prev, hty, x_new, partials, s); break;
-    default: st = launch_pgd<T, 8>(p, x, x_prev, hty, x_new, partials, s); break;
-  }
-  return st;
+  return with_radius<1>(R, [&](auto r) {
+    return launch_pgd<T, decltype(r)::value>(p, x, x_prev, hty, x_new, partials, s);
+  });
 }
 
 template <typename T>
@@ -1091,8 +1069,15 @@ struct PgdPlan {
   int R;
   PgdParams<float> pf;
   PgdParams<double> pd;
+  int64_t fold_rows, fold_per_row;  // of the parameters in use: the shape pxa_tile_partials_fold folds
   unsigned* counter;
 };
+
+// One launch from a plan, `args` being pgd_run's arguments after (p, R): the dtype choice of every plan-step form.
+template <typename... A>
+int plan_run(const PgdPlan* pl, A... args) {
+  return pl->dtype == PXA_F32 ? pgd_run<float>(pl->pf, pl->R, args...) : pgd_run<double>(pl->pd, pl->R, args...);
+}
 
 }  // namespace
 }  // namespace pxa
@@ -1124,10 +1109,15 @@ int pxa_pgd_tv2d_plan(int dtype, int64_t stack, int64_t y_images, int64_t n0, in
   PgdPlan* pl = new PgdPlan();
   pl->dtype = dtype;
   int e = PXA_ERR_DTYPE;
+  auto prepare = [&](auto& p) {
+    e = pgd_params(stack, y_images, n0, n1, nt0, off0, coef0, nt1, off1, coef1, h0, h1, lam, mu, prox, p, pl->R);
+    pl->fold_rows = p.fold_rows;
+    pl->fold_per_row = p.fold_per_row;
+  };
   if (dtype == PXA_F32)
-    e = pgd_params<float>(stack, y_images, n0, n1, nt0, off0, coef0, nt1, off1, coef1, h0, h1, lam, mu, prox, pl->pf, pl->R);
+    prepare(pl->pf);
   else if (dtype == PXA_F64)
-    e = pgd_params<double>(stack, y_images, n0, n1, nt0, off0, coef0, nt1, off1, coef1, h0, h1, lam, mu, prox, pl->pd, pl->R);
+    prepare(pl->pd);
   if (e == PXA_OK) {  // HIP failures: the positive hipError_t (the header's convention: HIP codes > 0, PXA_ERR_* < 0)
     hipError_t he = hipMalloc((void**)&pl->counter, sizeof(unsigned));
     if (he != hipSuccess) pl->counter = nullptr;
@@ -1148,11 +1138,8 @@ int pxa_pgd_tv2d_plan_step(void* plan, double a, double tau, double prox_w, cons
                            uint32_t* rel_flags, uint32_t seq, void* stream) {
   PXA_CHECK_ARG(plan != nullptr);
   const PgdPlan* pl = (const PgdPlan*)plan;
-  if (pl->dtype == PXA_F32)
-    return pgd_run<float>(pl->pf, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, x_ref, rel_values, rel_flags,
-                          seq, pl->counter, as_stream(stream));
-  return pgd_run<double>(pl->pd, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, x_ref, rel_values, rel_flags, seq,
-                         pl->counter, as_stream(stream));
+  return plan_run(pl, a, tau, prox_w, x, x_prev, hty, x_new, partials, x_ref, rel_values, rel_flags, seq, pl->counter,
+                  as_stream(stream));
 }
 
 int pxa_pgd_tv2d_plan_step_fold(void* plan, double a, double tau, double prox_w, const void* x, const void* x_prev,
@@ -1160,13 +1147,10 @@ int pxa_pgd_tv2d_plan_step_fold(void* plan, double a, double tau, double prox_w,
                                 uint32_t* rel_flags, uint32_t seq, void* stream) {
   PXA_CHECK_ARG(plan != nullptr && partials != nullptr && rel_values != nullptr && rel_flags != nullptr);
   const PgdPlan* pl = (const PgdPlan*)plan;
-  const int64_t stack = pl->dtype == PXA_F32 ? pl->pf.stack : pl->pd.stack;
-  const int64_t rows = stack / (pl->dtype == PXA_F32 ? pl->pf.y_images : pl->pd.y_images);
-  const int64_t per_row = (int64_t)(pl->dtype == PXA_F32 ? pl->pf.ntiles : pl->pd.ntiles) * (kThreads / 64) / rows;
-  const int e = pxa_pgd_tv2d_plan_step(plan, a, tau, prox_w, x, x_prev, hty, x_new, partials, x_ref, nullptr, nullptr,
-                                       0, stream);
-  if (e != PXA_OK) return e;
-  return pxa_tile_partials_fold(rows, per_row, partials, rel_values, rel_flags, seq, stream);
+  if (const int e = plan_run(pl, a, tau, prox_w, x, x_prev, hty, x_new, partials, x_ref, nullptr, nullptr, 0,
+                             pl->counter, as_stream(stream)))
+    return e;
+  return pxa_tile_partials_fold(pl->fold_rows, pl->fold_per_row, partials, rel_values, rel_flags, seq, stream);
 }
 
 int pxa_pgd_tv2d_plan_step_wfold(void* plan, double a, double tau, double prox_w, const void* x, const void* x_prev,
@@ -1174,18 +1158,10 @@ int pxa_pgd_tv2d_plan_step_wfold(void* plan, double a, double tau, double prox_w
                                  uint32_t seq, void* stream) {
   PXA_CHECK_ARG(plan != nullptr && partials != nullptr && rel_values != nullptr && rel_flags != nullptr);
   const PgdPlan* pl = (const PgdPlan*)plan;
-  const int64_t stack = pl->dtype == PXA_F32 ? pl->pf.stack : pl->pd.stack;
-  const int64_t rows = stack / (pl->dtype == PXA_F32 ? pl->pf.y_images : pl->pd.y_images);
-  const int64_t per_row = (int64_t)(pl->dtype == PXA_F32 ? pl->pf.ntiles : pl->pd.ntiles) * (kThreads / 64) / rows;
-  int e;
-  if (pl->dtype == PXA_F32)
-    e = pgd_run<float>(pl->pf, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0,
-                       pl->counter, as_stream(stream), 1);
-  else
-    e = pgd_run<double>(pl->pd, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0,
-                        pl->counter, as_stream(stream), 1);
-  if (e != PXA_OK) return e;
-  return pxa_tile_partials_fold(rows, per_row, partials, rel_values, rel_flags, seq, stream);
+  if (const int e = plan_run(pl, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0,
+                             pl->counter, as_stream(stream), 1))
+    return e;
+  return pxa_tile_partials_fold(pl->fold_rows, pl->fold_per_row, partials, rel_values, rel_flags, seq, stream);
 }
 
 int pxa_pgd_tv2d_plan_step_wpub(void* plan, double a, double tau, double prox_w, const void* x, const void* x_prev,
@@ -1194,11 +1170,8 @@ int pxa_pgd_tv2d_plan_step_wpub(void* plan, double a, double tau, double prox_w,
   PXA_CHECK_ARG(plan != nullptr && partials != nullptr);
   PXA_CHECK_ARG(prev_partials == nullptr || (rel_values != nullptr && rel_flags != nullptr));
   const PgdPlan* pl = (const PgdPlan*)plan;
-  if (pl->dtype == PXA_F32)
-    return pgd_run<float>(pl->pf, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0,
-                          pl->counter, as_stream(stream), 1, prev_partials, rel_values, rel_flags, seq);
-  return pgd_run<double>(pl->pd, pl->R, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0,
-                         pl->counter, as_stream(stream), 1, prev_partials, rel_values, rel_flags, seq);
+  return plan_run(pl, a, tau, prox_w, x, x_prev, hty, x_new, partials, nullptr, nullptr, nullptr, 0, pl->counter,
+                  as_stream(stream), 1, prev_partials, rel_values, rel_flags, seq);
 }
 
 int pxa_pgd_tv2d_plan_free(void* plan) {

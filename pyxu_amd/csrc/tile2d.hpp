@@ -325,5 +325,40 @@ __device__ inline unsigned xcd_tile(unsigned bid, unsigned nb) {
   return g8 * q8 + (g8 < r8 ? g8 : r8) + (bid >> 3);
 }
 
+// ------------------------------------------------------------------ host side: the taps of one axis
+// Dense tap window in double (index t + kMaxR) from (offset, coefficient) lists, coefficients of one offset added in
+// list order; returns the reach max |offset|, or -1 when it exceeds kMaxR (nothing is written then).
+using TapWindow = double[2 * kMaxR + 1];
+inline int tap_window(int nt, const int32_t* off, const double* coef, TapWindow& k) {
+  for (double& v : k) v = 0.0;
+  int R = 0;
+  for (int q = 0; q < nt; ++q) R = abs(off[q]) > R ? abs(off[q]) : R;
+  if (R > kMaxR) return -1;
+  for (int q = 0; q < nt; ++q) k[off[q] + kMaxR] += coef[q];
+  return R;
+}
+
+// The kernels' form of a window for radius R: w[t + R] = k[t], |t| <= R, zero beyond.
+template <typename T, int N>
+inline void tap_dense(const TapWindow& k, int R, T (&w)[N]) {
+  for (T& v : w) v = T(0);
+  for (int t = -R; t <= R; ++t) w[t + R] = (T)k[t + kMaxR];
+}
+
+// Interior taps of G = H^T H for radius R: g[d + 2 R] = sum_t k[t] k[t + d], |d| <= 2 R, zero beyond.  Summed in
+// double over t ascending (terms outside [-R, R] skipped), then one cast: both fused steps derive G from here.
+template <typename T>
+inline void tap_autocorr(const TapWindow& k, int R, T (&g)[kMaxG]) {
+  for (T& v : g) v = T(0);
+  for (int d = -2 * R; d <= 2 * R; ++d) {
+    double s = 0.0;
+    for (int t = -R; t <= R; ++t) {
+      if (t + d < -R || t + d > R) continue;
+      s += k[t + kMaxR] * k[t + d + kMaxR];
+    }
+    g[d + 2 * R] = (T)s;
+  }
+}
+
 }  // namespace tile2d
 }  // namespace pxa
