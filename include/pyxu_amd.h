@@ -304,6 +304,49 @@ int pxa_nlcg_direction(int dtype, int variant, int restart, int64_t rows, int64_
 int pxa_ls_armijo(int dtype, int64_t rows, const void* f_trial, const void* f_x, const double* gp, int32_t nb, double c,
                   double r, void* a, int32_t* trials, uint32_t* nfail_host, uint32_t* flag, uint32_t seq, void* stream);
 
+/* ProxAdam (opt/solver/prox_adam.py:332-416) for `rows` <= 65535 stacked problems of n entries.  Row r is split
+ * over nb = pxa_proxadam_blocks(rows, n) workgroups (blocks_per_row: up to 1024), workgroup b owning elements
+ * [b chunk, (b + 1) chunk), chunk = ceil(n / nb) rounded up to a whole 16-byte vector.  16-byte accesses when every
+ * operand is 16-byte aligned and (rows == 1 or n is a whole number of vectors), scalar accesses otherwise.
+ * `work`: pxa_proxadam_workspace_bytes(rows, n) bytes: five planes of rows * nb doubles (the psi maxima; two pairs
+ * of RelError partials, used alternately), rows doubles (psimax), rows int32 state words, two int32 counters.
+ *
+ * pxa_proxadam_moments: one launch for everything between g = grad f(x) and x' (prox_adam.py:341-370); the scalars
+ * are cast to the working type T, omb1 / omb2 are 1 - b1 / 1 - b2 and c1 = 1 - b1^t, c2 = sqrt(1 - b2^t) the bias
+ * corrections, all formed by the caller in T:
+ *   m' = b1 m + omb1 g;  v' = max(b2 v + omb2 g^2, eps_var);  vhat' = first ? v' : max(vhat, v')  (NaN-propagating)
+ *   variant 0 (adam):    phi = m' / c1,  psi = sqrt(v') / c2 + eps_adam
+ *   variant 1 (amsgrad): phi = m',       psi = sqrt(vhat')
+ *   variant 2 (padam):   phi = m',       psi = vhat'^p  (sqrt when p == 0.5)
+ *   x' = x - a (phi / psi)
+ * m_out / v_out / vhat_out may be m / v / vhat; x_out is none of the other operands; vhat may be NULL when `first`.
+ * psi_out != NULL: psi is stored too and the first plane of `work` receives the per-workgroup maxima of psi. */
+int pxa_proxadam_blocks(int64_t rows, int64_t n);
+size_t pxa_proxadam_workspace_bytes(int64_t rows, int64_t n);
+int pxa_proxadam_moments(int dtype, int variant, int first, int64_t rows, int64_t n, double b1, double omb1, double b2,
+                         double omb2, double eps_var, double c1, double c2, double eps_adam, double a, double p,
+                         const void* g, const void* m, const void* v, const void* vhat, const void* x, void* m_out,
+                         void* v_out, void* vhat_out, void* x_out, void* psi_out, void* work, void* stream);
+
+/* The metric prox  min_z g(z) + 1 / (2 a) ||z - xt||^2_diag(psi)  of every row by accelerated PGD (the reference's
+ * per-row PGD with tau = gamma = a / max(psi), d = 75 and a RelError(eps) stop at rate 1), all rows per launch.
+ * pxa_proxadam_sub_init (after pxa_proxadam_moments with psi_out): psimax per row from the partial maxima, state
+ * words and counters cleared.  pxa_proxadam_sub_step, launch k = 1, 2, ... with mom = (k - 1) / (k + 75): a row
+ * whose state word holds an earlier launch does nothing.  Otherwise, for k >= 2, the partials of launch k - 1 are
+ * folded in a fixed order to num = sum (z - z_prev)^2 and den = sum z_prev^2; if sqrt(num) <= eps sqrt(den) the row is
+ * finished: z is copied to its row of `out` and its state word becomes k (z is sub-iterate k - 1).  Else
+ *   y = (z - z_prev) mom + z;  r = psi / psimax;  w = (1 - r) y + r xt;  z_new = prox(w)
+ * and the partials of sum (z_new - z)^2 and sum z^2 are left for launch k + 1.  Launch 1 takes z = z_prev = xt.  kind:
+ *   1  lam ||.||_1, pw = lam: soft threshold at (a / psimax) lam      2  z >= 0: clip(w, 0, None)
+ *   3  lam ||.||_1 + (z >= 0), pw = lam: clip(w - (a / psimax) lam, 0, None)      4  |z| <= pw: clip(w, -pw, pw)
+ * The number of rows that computed an update goes to *nrun_host, then `seq` to *flag (pxa_host_alloc memory,
+ * system-scope release).  A launch after every row has finished changes nothing but these two words.  z_new and `out`
+ * alias no other operand.  No floating-point atomics: the same calls give the same bits. */
+int pxa_proxadam_sub_init(int64_t rows, int64_t n, void* work, void* stream);
+int pxa_proxadam_sub_step(int dtype, int kind, int k, int64_t rows, int64_t n, double mom, double eps, double a,
+                          double pw, const void* xt, const void* psi, const void* z_prev, const void* z, void* z_new,
+                          void* out, void* work, uint32_t* nrun_host, uint32_t* flag, uint32_t seq, void* stream);
+
 /* RelError statistics from the fused PGD step's per-tile partials (pxa_pgd_tv2d_step[_y] with
  * `partials`): out[0 * rows + r] = sum (x_new - x)^2 and out[1 * rows + r] = sum x^2 over the per_row
  * consecutive tiles of stack row r, fixed summation order.  At stop_rate 1 the criterion's stored x_prev

@@ -710,6 +710,133 @@ def ls_failed(fb, seq):
     return int(fb.values.view(np.uint32)[0])
 
 
+PROXADAM_VARIANTS = {"adam": 0, "amsgrad": 1, "padam": 2}  # pxa_proxadam_moments variants
+PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX = 1, 2, 3, 4  # pxa_proxadam_sub_step prox kinds
+
+
+def proxadam_blocks(rows, n):
+    """Workgroups (= partials) per row of the ProxAdam kernels."""
+    return int(lib.pxa_proxadam_blocks(int(rows), int(n)))
+
+
+def proxadam_workspace(rows, n, like):
+    """A float64 device tensor of pxa_proxadam_workspace_bytes(rows, n) bytes."""
+    need = int(lib.pxa_proxadam_workspace_bytes(int(rows), int(n)))
+    return _torch().empty(((need + 7) // 8,), dtype=_torch().float64, device=like.device)
+
+
+def proxadam_work_views(work, rows, n):
+    """(psi partial maxima (rows, nb), psimax (rows,), state words int32 (rows,)) of a ProxAdam workspace."""
+    nb = proxadam_blocks(rows, n)
+    tail = work[5 * rows * nb + rows:].view(_torch().int32)
+    return work[: rows * nb].reshape(rows, nb), work[5 * rows * nb: 5 * rows * nb + rows], tail[:rows]
+
+
+def proxadam_stat_partials(work, rows, n, k):
+    """The (2, rows, nb) partials sum (z_new - z)^2 / sum z^2 that sub-step launch `k` left."""
+    nb = proxadam_blocks(rows, n)
+    off = rows * nb * (1 + 2 * (k & 1))
+    return work[off: off + 2 * rows * nb].reshape(2, rows, nb)
+
+
+def _proxadam_operand(t, name, rows, n, like):
+    """A contiguous (rows, n) device operand of like's dtype, taken as it is (views may start off a 16-byte
+    boundary: the kernels then take their scalar path)."""
+    if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dtype == like.dtype
+            and tuple(t.shape) == (rows, n)):
+        raise ValueError(f"proxadam: {name} must be a contiguous ({rows}, {n}) device tensor of dtype {like.dtype}")
+    return t
+
+
+def _proxadam_work_check(work, rows, n, where):
+    need = int(lib.pxa_proxadam_workspace_bytes(rows, n))
+    if work.dtype != _torch().float64 or not work.is_cuda or not work.is_contiguous() or work.numel() * 8 < need:
+        raise ValueError(f"{where}: work must be a contiguous float64 device tensor of >= {need} bytes")
+
+
+def proxadam_moments(variant, first, g, m, v, vhat, x, m_out, v_out, vhat_out, x_out, b1, omb1, b2, omb2, eps_var, c1,
+                     c2, eps_adam, a, p, psi_out=None, work=None):
+    """pxa_proxadam_moments on (rows, n) operands: the ProxAdam moment update and gradient step in one launch
+    (include/pyxu_amd.h).  m_out / v_out / vhat_out may be m / v / vhat; x_out is a buffer of its own; vhat may be
+    None when `first`.  With psi_out, psi is stored and `work` (proxadam_workspace) receives its partial maxima."""
+    if variant not in PROXADAM_VARIANTS.values():
+        raise ValueError(f"proxadam_moments: unknown variant {variant}")
+    if g.dim() != 2:
+        raise ValueError("proxadam_moments: operands must be (rows, n) tensors")
+    dtcode(g)
+    rows, n = g.shape
+    if not (1 <= rows <= 65535 and n >= 1):
+        raise ValueError(f"proxadam_moments: rows must be in [1, 65535] and n >= 1, got {(rows, n)}")
+    ops = dict(g=g, m=m, v=v, x=x, m_out=m_out, v_out=v_out, vhat_out=vhat_out, x_out=x_out)
+    if not first or vhat is not None:
+        ops["vhat"] = vhat
+    if psi_out is not None:
+        ops["psi_out"] = psi_out
+    for name, t in ops.items():
+        if t is None:
+            raise ValueError(f"proxadam_moments: {name} is missing")
+        _proxadam_operand(t, name, rows, n, g)
+    others = [t.data_ptr() for k, t in ops.items() if k != "x_out"]
+    if x_out.data_ptr() in others:
+        raise ValueError("proxadam_moments: x_out must not alias another operand")
+    if psi_out is not None:
+        if psi_out.data_ptr() in [t.data_ptr() for k, t in ops.items() if k != "psi_out"]:
+            raise ValueError("proxadam_moments: psi_out must not alias another operand")
+        if work is None:
+            raise ValueError("proxadam_moments: psi_out needs the workspace")
+        _proxadam_work_check(work, rows, n, "proxadam_moments")
+    check(lib.pxa_proxadam_moments(dtcode(g), int(variant), int(bool(first)), rows, n, float(b1), float(omb1), float(b2),
+                                   float(omb2), float(eps_var), float(c1), float(c2), float(eps_adam), float(a), float(p),
+                                   ptr(g), ptr(m), ptr(v), ptr(vhat) if vhat is not None else None, ptr(x), ptr(m_out),
+                                   ptr(v_out), ptr(vhat_out), ptr(x_out), ptr(psi_out) if psi_out is not None else None,
+                                   work.data_ptr() if work is not None else None, stream()), "pxa_proxadam_moments")
+    return x_out
+
+
+def proxadam_sub_init(rows, n, work):
+    """pxa_proxadam_sub_init: psimax per row from the partial maxima pxa_proxadam_moments left in `work`; state words
+    and counters cleared."""
+    rows, n = int(rows), int(n)
+    if not (1 <= rows <= 65535 and n >= 1):
+        raise ValueError(f"proxadam_sub_init: rows must be in [1, 65535] and n >= 1, got {(rows, n)}")
+    _proxadam_work_check(work, rows, n, "proxadam_sub_init")
+    check(lib.pxa_proxadam_sub_init(rows, n, work.data_ptr(), stream()), "pxa_proxadam_sub_init")
+
+
+def proxadam_sub_step(kind, k, mom, eps, a, pw, xt, psi, z_prev, z, z_new, out, work, fb):
+    """pxa_proxadam_sub_step: sub-iteration `k` (1-based; z = z_prev = xt at k == 1) of the metric prox on every row
+    that still runs (include/pyxu_amd.h).  fb: a HostFlagBuffer(1, 1, 1) that receives the number of rows that
+    computed an update (proxadam_running(fb, seq) reads it).  Returns the publication's sequence number."""
+    if kind not in (PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX):
+        raise ValueError(f"proxadam_sub_step: unknown prox kind {kind}")
+    if xt.dim() != 2:
+        raise ValueError("proxadam_sub_step: operands must be (rows, n) tensors")
+    dtcode(xt)
+    rows, n = xt.shape
+    if not (1 <= rows <= 65535 and n >= 1 and int(k) >= 1):
+        raise ValueError(f"proxadam_sub_step: rows must be in [1, 65535], n >= 1 and k >= 1, got {(rows, n, k)}")
+    ops = dict(xt=xt, psi=psi, z_prev=z_prev, z=z, z_new=z_new, out=out)
+    for name, t in ops.items():
+        _proxadam_operand(t, name, rows, n, xt)
+    for name in ("z_new", "out"):
+        if ops[name].data_ptr() in [t.data_ptr() for q, t in ops.items() if q != name]:
+            raise ValueError(f"proxadam_sub_step: {name} must not alias another operand")
+    _proxadam_work_check(work, rows, n, "proxadam_sub_step")
+    if not isinstance(fb, HostFlagBuffer) or len(fb.values) < 1 or len(fb.flags) != 1:
+        raise ValueError("proxadam_sub_step: fb must be a HostFlagBuffer(1, 1, 1)")
+    seq = fb.next_seq()
+    check(lib.pxa_proxadam_sub_step(dtcode(xt), int(kind), int(k), rows, n, float(mom), float(eps), float(a), float(pw),
+                                    ptr(xt), ptr(psi), ptr(z_prev), ptr(z), ptr(z_new), ptr(out), work.data_ptr(),
+                                    fb.vptr, fb.fptr, seq, stream()), "pxa_proxadam_sub_step")
+    return seq
+
+
+def proxadam_running(fb, seq):
+    """Number of rows that computed an update in the sub-step launch of publication `seq` (waits for its flag)."""
+    fb.wait(seq)
+    return int(fb.values.view(np.uint32)[0])
+
+
 def dense_normal_pfold(A, r, p, p_new, rr, rr_out, fb, seq, s, d, work, pdot):
     """pxa_dense_normal_pdot_pfold: p_new = r + beta p (the CG's previous p update, beta from cg_update_xr's ||r'||^2
     partials at pdot + 64 doubles and `rr`), then Y = s A^T (A p_new) + d p_new and the <p_new, Y> partials into

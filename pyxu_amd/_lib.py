@@ -64,6 +64,13 @@ EXPORTS = {
     "pxa_nlcg_workspace_bytes": (sz, [i64]),
     "pxa_nlcg_direction": (i32, [i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ct.c_uint32, vp, vp]),
     "pxa_ls_armijo": (i32, [i32, i64, vp, vp, vp, ct.c_int32, f64, f64, vp, vp, vp, vp, ct.c_uint32, vp]),
+    "pxa_proxadam_blocks": (i32, [i64, i64]),
+    "pxa_proxadam_workspace_bytes": (sz, [i64, i64]),
+    "pxa_proxadam_moments": (i32, [i32, i32, i32, i64, i64, f64, f64, f64, f64, f64, f64, f64, f64, f64, f64, vp, vp, vp,
+                                   vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pxa_proxadam_sub_init": (i32, [i64, i64, vp, vp]),
+    "pxa_proxadam_sub_step": (i32, [i32, i32, i32, i64, i64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    ct.c_uint32, vp]),
     "pxa_stencil_axis": (i32, [i32, i64, i32, P_i64, i32, i32, P_i32, P_f64, i32, vp, i64, vp, i64, f64, vp]),
     "pxa_stencil_sep_workspace_bytes": (sz, [i32, i64, i32, P_i64, P_int]),
     "pxa_stencil_sep": (i32, [i32, i64, i32, P_i64, P_int, P_i32, P_f64, vp, i64, vp, i64, f64, vp, vp]),
