@@ -635,7 +635,7 @@ int pxa_pgd_tv2d_plan_step_wpub(void* plan, double a, double tau, double prox_w,
 int pxa_pgd_tv2d_plan_free(void* plan);
 int pxa_pgd_tv2d_last_kernel(void);
 /* Diagnostics: s_memtime stamps of the tile kernel's last launch under PXA_TUNE_PGD_DIAG bit 5
- * (workgroups 0, 1, grid/2, grid-1; waves 0..3; 8 phase points; n <= 128 words). */
+ * (workgroups 0, 9, grid/2 + 8, grid-1; waves 0..3; 8 phase points; n <= 128 words). */
 int pxa_pgd_tile_trace(uint64_t* host_out, int n);
 int pxa_pgd_tv2d_step(int dtype, int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0, const int32_t* off0,
                       const double* coef0, int nt1, const int32_t* off1, const double* coef1, double h0, double h1,

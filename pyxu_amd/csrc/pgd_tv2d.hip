@@ -28,10 +28,12 @@
 //   pass A   PT = (G0 yk) on the tile rows, all A columns, stored TRANSPOSED ([col][row])   (V x V
 //                 register blocks: ds_read_b128 rows, packed FMAs, ds_write_b128 columns)
 //   pass B   out = G1 along each row (sweeps PT rows = image columns) - b + Grad^T q, prox, store;
-//                 q is evaluated on the fly from yk in A (5 x 3 stencil of yk per 4 x 2 block).
+//                 q is evaluated on the fly from yk in A.  fp32: one 2-row x 4-column block per thread, swept over
+//                 ds_read_b64 rows of PT and finished in that thread's registers as two 16-B row vectors
+//                 (pass_b_blocks); fp64: 2 x 1 items staged through LDS into a row-major epilogue (pass_b_staged).
 // LDS pitches / lane orders are conflict-free for R = 6 fp32 under the MI355X_MICROARCH.md §LDS
-// bank model (scripts/ldsbank.py).  The blockIdx -> tile map is XCD-aware: each of the 8 XCDs owns a
-// contiguous band of tiles so that halo re-reads of x / x_prev hit its own L2.
+// bank model (scripts/ldsbank.py, scripts/ldsbank_blocks.py).  The blockIdx -> tile map is XCD-aware: each of the
+// 8 XCDs owns a contiguous band of tiles so that halo re-reads of x / x_prev hit its own L2.
 #include "tile2d.hpp"
 #include <type_traits>
 
@@ -107,7 +109,7 @@ struct PgdParams {
 // saves; it was removed.
 
 // Timing trace (PXA_TUNE_PGD_DIAG bit 5, read by pxa_pgd_tile_trace): s_memtime stamps of waves 0-3 of
-// workgroups 0, 1, grid/2 and grid-1, 8 points of their tile.  Staged in LDS beyond the kernel's own
+// workgroups 0, 9, grid/2 + 8 and grid-1, 8 points of their tile.  Staged in LDS beyond the kernel's own
 // carve, dumped at exit.
 constexpr int kTraceWords = 4 * 4 * 8;
 __device__ unsigned long long g_tile_trace[kTraceWords];
@@ -303,17 +305,21 @@ __device__ inline void win_store(const PgdParams<T>& p, T* A, const Window<T, R>
   }
 }
 
+// Pitch of PT: fp32 runs pass B on 2 x 4 row-major blocks (tile2d.hpp BlockB), fp64 on Layout's 2 x 1 items.
+template <typename T, int R>
+__host__ __device__ constexpr int pt_pitch() {
+  if constexpr (sizeof(T) == 4) return BlockB<T, R>::PTP;
+  else return Layout<T, R>::PTP;
+}
+
 // ---- pass A: PT[col][row] = (G0 yk)[row][col] for the TY tile rows and all A columns
 template <typename T, int R, bool EDGE, int D = 0>
 __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T* KT, int ty0, int tid = threadIdx.x) {
   using L = Layout<T, R>;
   constexpr int V = L::V;
   constexpr int KA = cdiv(L::NPA, kThreads);
-  // one item per thread (fp32): items spread over all 4 waves in chunks of a multiple of NA, so each
-  // lane keeps it % NA == lane % NA (the conflict-free lane pattern) -- e.g. 48 / 48 / 48 / 32 for the
-  // 176 items of R = 6, where consecutive numbering leaves wave 3 idle through pass A
-  constexpr int CH = KA == 1 ? rup(cdiv(L::NPA, kThreads / 64), L::NA) : 64;
-  static_assert(KA > 1 || CH <= 64, "pass-A chunk fits a wave");
+  // one item per thread (fp32), in thread order: the 176 items of R = 6 fill waves 0, 1 and three quarters of wave 2; wave 3
+  // has none.  Spreading them over four waves would issue four wave-passes instead of three for the same work.
   const bool edge_rows = EDGE && (ty0 < R || ty0 + TY > p.n0 - R);
 #pragma unroll
   for (int k = 0; k < KA; ++k) {
@@ -328,53 +334,41 @@ __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T*
         T colv[V];
 #pragma unroll
         for (int u = 0; u < V; ++u) colv[u] = acc[u][v];
-        st_vec<T, V>(PT + (V * b + v) * L::PTP + V * a, colv);
+        st_vec<T, V>(PT + (V * b + v) * pt_pitch<T, R>() + V * a, colv);
       }
     }
   }
 }
 
-// ---- TV dual once per pixel (fp32 lane map of pass B; PXA_PGD_TVX=0 builds the 5 x 3 window path for A/B).  Pass B's item (4 rows x 2
-// columns) needs q at its own 8 pixels, q0 one row above and q1 one column to the left; the default path
-// evaluates q on the 5 x 3 window (15 per item, 1.9 x per pixel).  Here an item evaluates its own 8, writes
-// its last row's q0 and last column's q1 to an exchange area in A's rows that pass B no longer reads, lanes
-// 0..47 of the wavefront evaluate the wavefront's halo (16 q0 of the tile row above, 32 q1 of the column to the
-// left of the wavefront's 16 columns), and every item reads its neighbours' values back.  Same q expressions,
-// same bits.  Within one wavefront (items (a, cb) of a wavefront: all 8 row groups x 8 column items) LDS
-// accesses execute in order, so no barrier is needed.  Interleaved A/B (r05zj, profiles/r05zj_pgd_tvx_ab.txt):
-// bit-identical at 2048^2 and 1000 x 1500; kernel 23.5 -> 23.3 us at 2048^2, C5 0.657 -> 0.651 ms, 4096^2 76.6 ->
-// 72.9 us: the VALU saved is partly spent on the exchange's LDS traffic.
-#ifndef PXA_PGD_TVX
-#define PXA_PGD_TVX 1
-#endif
-constexpr int kTvxFloats = 9 * 16 + 9 * 32;  // per wavefront: q0 [row group + 1][16 cols], q1 [col item + 1][32 rows]
+__device__ inline void st_pair(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
+
+// ---- TV dual of a pass-B block (fp32): Grad^T q at the block's own 2 x 4 pixels needs q there, q0 one row above
+// (4 values) and q1 one column to the left (2 values).
+// Exchange form (R >= 6, where A's rows above / below the TV stencil's reach hold it): q is evaluated once per pixel.
+// A block evaluates its own 8, writes its last row's q0 and last column's q1 to an exchange area in A's rows that
+// pass B no longer reads, lanes 0..47 of the wave evaluate the wave's halo (32 q0 of the row above its 16 x 32
+// region, 16 q1 of the column to its left), and every block reads its neighbours' values back.  Within one wave LDS
+// accesses execute in order, so no barrier and no drain is needed between the stores and the reads.
+// Window form (smaller R): q on the block's 3 x 5 window (15 evaluations for 8 pixels).
+// Same q expressions in both, the same as the fp64 items': same bits.
+// per wave: q0 [row pair + 1][32 cols at pitch 40: the row pairs of a ds_read_b128 lane group, two apart, are 16 banks
+// apart], q1 [col item + 1][16 rows]
+constexpr int kTvxP0 = 40;
+template <typename T, int R>
+constexpr int kTvxFloats = 9 * kTvxP0 + 9 * BlockB<T, R>::WR;
 
 template <typename T, int R, bool EDGE>
-__device__ inline void tv_exchange(const PgdParams<T>& p, T* A, int ty0, int tx0, int tid, int a, int cb,
-                                   T (&yc)[kVecN<T>][2], T (&tv)[kVecN<T>][2]) {
+__device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, int wv, int ln, T (&yc)[2][4],
+                                T (&tv)[2][4]) {
   using L = Layout<T, R>;
-  constexpr int V = L::V;
-  constexpr int CA = L::CA;
+  using B = BlockB<T, R>;
+  constexpr int CA = L::CA, AP = L::AP;
+  constexpr bool kExchange = (2 * R - 1) * AP >= 2 * kTvxFloats<T, R>;
   const int n0 = p.n0, n1 = p.n1;
-  const int lane = tid & 63, wv = tid >> 6, cbl = cb & 7;
-  const int c0 = 2 * cb;
-  // own rows (window rows 1..V) and the row below, columns c0 .. c0 + 2
-  T y[V + 1][3];
-#pragma unroll
-  for (int r = 0; r <= V; ++r) {
-    const T* arow = A + (V * a + r + 2 * R) * L::AP + CA + c0;
-    T mid[2], hi[2];
-    ld_pair<T>(arow, mid);
-    ld_pair<T>(arow + 2, hi);
-    y[r][0] = mid[0];
-    y[r][1] = mid[1];
-    y[r][2] = hi[0];
-  }
-#pragma unroll
-  for (int u = 0; u < V; ++u)
-#pragma unroll
-    for (int w = 0; w < 2; ++w) yc[u][w] = y[u][w];
-  if (!p.tv) return;
+  int rpl, cil, wr0, wc0;
+  B::item(wv, ln, rpl, cil, wr0, wc0);
+  const int r0 = wr0 + 2 * rpl, c0 = wc0 + 4 * cil;  // the block's first pixel (tile-relative)
+  const T* own = A + (r0 + 2 * R) * AP + CA + c0;
   auto qat = [&](T yc_, T ydn, T yrt, int gr, int gc, T& q0, T& q1) {
     const T v0 = fma(p.g0a, yc_, p.g0b * ydn);
     const T v1 = fma(p.g1a, yc_, p.g1b * yrt);
@@ -383,56 +377,114 @@ __device__ inline void tv_exchange(const PgdParams<T>& p, T* A, int ty0, int tx0
     q0 = v0 * w;
     q1 = v1 * w;
   };
-  T q0[V][2], q1[V][2];
+  if constexpr (kExchange) {
+    // own rows and the row below (16-B vectors), the column to the right of the own rows
+    T y[3][5];
 #pragma unroll
-  for (int u = 0; u < V; ++u)
+    for (int r = 0; r < 3; ++r) {
+      T m[4];
+      ld_vec<T, 4>(own + r * AP, m);
 #pragma unroll
-    for (int w = 0; w < 2; ++w)
-      qat(y[u][w], y[u + 1][w], y[u][w + 1], ty0 + V * a + u, tx0 + c0 + w, q0[u][w], q1[u][w]);
-  // exchange area of this wavefront: waves 0, 1 in A's top dead rows, 2, 3 in the bottom ones
-  T* E = (wv < 2 ? A : A + (TY + 2 * R + 1) * L::AP) + (wv & 1) * kTvxFloats;
-  T* E0 = E;            // [a + 1][col within the wavefront's 16]
-  T* E1 = E + 9 * 16;   // [col item + 1][row]
-  // halo of the wavefront: lanes 0..15 the q0 of tile row -1 (its 16 columns), lanes 16..47 the q1 of the column
-  // left of its first column (tile rows 0..31)
-  if (lane < 48) {
-    T hq0, hq1;
-    if (lane < 16) {
-      const int tc = 16 * wv + lane;
-      const T* r0 = A + (2 * R - 1) * L::AP + CA + tc;
-      qat(r0[0], r0[L::AP], r0[1], ty0 - 1, tx0 + tc, hq0, hq1);
-      E0[lane] = hq0;
-    } else {
-      const int j = lane - 16, tc = 16 * wv - 1;
-      const T* r0 = A + (j + 2 * R) * L::AP + CA + tc;
-      qat(r0[0], r0[L::AP], r0[1], ty0 + j, tx0 + tc, hq0, hq1);
-      E1[j] = hq1;
+      for (int w = 0; w < 4; ++w) y[r][w] = m[w];
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      T hi[2];
+      ld_pair<T>(own + r * AP + 4, hi);
+      y[r][4] = hi[0];
+    }
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) yc[u][w] = y[u][w];
+    if (!p.tv) return;
+    T q0[2][4], q1[2][4];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int w = 0; w < 4; ++w)
+        qat(y[u][w], y[u + 1][w], y[u][w + 1], ty0 + r0 + u, tx0 + c0 + w, q0[u][w], q1[u][w]);
+    // exchange area of this wave: waves 0, 1 (tile rows 0..15) in A's top dead rows, 2, 3 in the bottom ones
+    T* E0 = (wv < 2 ? A : A + (TY + 2 * R + 1) * AP) + (wv & 1) * kTvxFloats<T, R>;  // [row pair + 1][col of the 32]
+    T* E1 = E0 + 9 * kTvxP0;                                                         // [col item + 1][row of the 16]
+    if (ln < 48) {
+      T hq0, hq1;
+      if (ln < 32) {  // q0 of the row above the region
+        const int tc = wc0 + ln;
+        const T* h = A + (wr0 - 1 + 2 * R) * AP + CA + tc;
+        qat(h[0], h[AP], h[1], ty0 + wr0 - 1, tx0 + tc, hq0, hq1);
+        E0[ln] = hq0;
+      } else {  // q1 of the column left of the region
+        const int j = ln - 32, tc = wc0 - 1;
+        const T* h = A + (wr0 + j + 2 * R) * AP + CA + tc;
+        qat(h[0], h[AP], h[1], ty0 + wr0 + j, tx0 + tc, hq0, hq1);
+        E1[j] = hq1;
+      }
+    }
+    st_vec<T, 4>(E0 + (rpl + 1) * kTvxP0 + 4 * cil, q0[1]);
+    st_pair(E1 + (cil + 1) * B::WR + 2 * rpl, q1[0][3], q1[1][3]);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");  // the compiler keeps the reads below behind the stores above
+    T up[4], left[2];
+    ld_vec<T, 4>(E0 + rpl * kTvxP0 + 4 * cil, up);
+    ld_pair<T>(E1 + cil * B::WR + 2 * rpl, left);
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const T qa = u == 0 ? up[w] : q0[0][w];
+        const T ql = w == 0 ? left[u] : q1[u][w - 1];
+        const T t0 = fma(p.g0b, qa, p.g0a * q0[u][w]);
+        const T t1 = fma(p.g1b, ql, p.g1a * q1[u][w]);
+        tv[u][w] = t0 + t1;
+      }
+  } else {
+    // yk window rows r0 - 1 .. r0 + 2, columns c0 - 1 .. c0 + 4, streamed two rows at a time so that the stencil keeps
+    // ~25 values live instead of the whole 4 x 6 window
+    auto yrow = [&](int r, T(&y)[6]) {
+      const T* arow = own + (r - 1) * AP;
+      T m[4];
+      ld_vec<T, 4>(arow, m);
+      y[0] = arow[-1];
+#pragma unroll
+      for (int w = 0; w < 4; ++w) y[w + 1] = m[w];
+      y[5] = arow[4];
+    };
+    // q at window row r, columns c0 - 1 .. c0 + 3, from yk rows r (yr) and r + 1 (yn)
+    auto qrow = [&](int r, const T(&yr)[6], const T(&yn)[6], T(&q0)[5], T(&q1)[5]) {
+#pragma unroll
+      for (int c = 0; c < 5; ++c) qat(yr[c], yn[c], yr[c + 1], ty0 + r0 - 1 + r, tx0 + c0 - 1 + c, q0[c], q1[c]);
+    };
+    T yr[6], yn[6];
+    yrow(0, yr);
+    yrow(1, yn);
+    T qp0[5], qp1[5];
+    if (p.tv) qrow(0, yr, yn, qp0, qp1);
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int c = 0; c < 6; ++c) yr[c] = yn[c];  // window row u + 1
+      yrow(u + 2, yn);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) yc[u][w] = yr[w + 1];
+      if (p.tv) {
+        T qc0[5], qc1[5];
+        qrow(u + 1, yr, yn, qc0, qc1);
+        // Grad^T q: flipped 2-tap adjoints, (+1/h tap at i - e_d) then (-1/h tap at i), summed over d
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const T t0 = fma(p.g0b, qp0[w + 1], p.g0a * qc0[w + 1]);
+          const T t1 = fma(p.g1b, qc1[w], p.g1a * qc1[w + 1]);
+          tv[u][w] = t0 + t1;
+        }
+#pragma unroll
+        for (int c = 0; c < 5; ++c) qp0[c] = qc0[c];
+      }
     }
   }
-  {
-    const T b[2] = {q0[V - 1][0], q0[V - 1][1]};
-    st_vec<T, 2>(E0 + (a + 1) * 16 + 2 * cbl, b);
-    const T c[4] = {q1[0][1], q1[1][1], q1[2][1], q1[3][1]};
-    st_vec<T, 4>(E1 + (cbl + 1) * 32 + 4 * a, c);
-  }
-  __builtin_amdgcn_wave_barrier();
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  T up[2], left[4];
-  ld_vec<T, 2>(E0 + a * 16 + 2 * cbl, up);
-  ld_vec<T, 4>(E1 + cbl * 32 + 4 * a, left);
-#pragma unroll
-  for (int u = 0; u < V; ++u)
-#pragma unroll
-    for (int w = 0; w < 2; ++w) {
-      const T qa = u == 0 ? up[w] : q0[u - 1][w];
-      const T ql = w == 0 ? left[u] : q1[u][0];
-      const T t0 = fma(p.g0b, qa, p.g0a * q0[u][w]);
-      const T t1 = fma(p.g1b, ql, p.g1a * q1[u][w]);
-      tv[u][w] = t0 + t1;
-    }
 }
 
-// ---- pass B: G1 along rows + Grad^T q, handed per output row-run to
+// ---- pass B on Layout's items (fp64): G1 along rows + Grad^T q, handed per output row-run to
 // `emit(k, u, gr, gc, g, yc)`: g = (G yk + Grad^T q) at row gr, columns gc .. gc + CW - 1 of item k,
 // yc = yk there.  The emitter finishes the pixels in place (finish_run) or stages g for the
 // coalesced epilogue (epilogue_staged).
@@ -488,11 +540,7 @@ __device__ inline void pass_b(const PgdParams<T>& p, const T* A, const T* PT, co
       };
       T yc[V][CW];  // yk at the item's own pixels
       T tv[V][CW];
-      constexpr bool kX = PXA_PGD_TVX && sizeof(T) == 4 && L::NA == 8 && CW == 2 && KB == 1 &&
-                          (2 * R - 1) * L::AP >= kTvxFloats * 2;
-      if constexpr (kX) {
-        tv_exchange<T, R, EDGE>(p, const_cast<T*>(A), ty0, tx0, tid, a, cb, yc, tv);
-      } else {
+      {
         T yr[CW + 2], yn[CW + 2];
         yrow(0, yr);
         yrow(1, yn);
@@ -537,7 +585,7 @@ __device__ inline void pass_b(const PgdParams<T>& p, const T* A, const T* PT, co
   }
 }
 
-// ---- staged epilogue: every thread parks g = G yk + Grad^T q of its pass-B pixels in O (the PT
+// ---- staged epilogue (fp64): every thread parks g = G yk + Grad^T q of its pass-B pixels in O (the PT
 // region, free once all G1 sweeps are done), then the workgroup finishes the tile in row-major order:
 // each 16-B vector of a row is one lane (16 lanes per fp32 row), so the H^T y / x loads and the x_new
 // stores are full 128-B lines instead of the pass-B item order's 64-B row pieces (measured on MI355X: a
@@ -647,45 +695,123 @@ __device__ inline void wave_partials(double part_d, double part_x, double* parti
   }
 }
 
-// Rows in flight per G sweep (tile2d.hpp sweep's D): 0 = compiler-scheduled (default); A/B builds limit it
-#ifndef PXA_PGD_SWEEP_DEPTH
-#define PXA_PGD_SWEEP_DEPTH 0
-#endif
+// ---- pass B and the epilogue of the fp32 tile on 2 x 4 row-major blocks (tile2d.hpp BlockB): one block per thread,
+// G1 swept along the block's 4 columns over b64 rows of PT (its two tile rows), Grad^T q from tv_block, then the block's
+// two 16-B row vectors are finished in registers: H^T y (and x for the RelError partials) loaded straight into the
+// lane that stores x_new.  H^T y is loaded behind the TV chain, so that the sweep covers its latency; x (RelError
+// partials only) behind the sweep.
+// The sweep has two forms, chosen by what the kernel's registers allow (scripts/pgd_window_isa.py --all):
+//   R >= 4  sweep_w: all 4R + 4 PT rows read back to back as single ds_read_b64 and held at once (2 VGPRs each), the FMAs
+//           compiler-scheduled behind counted waits.  The fastest form measured at R = 6 (profiles/pgd_blocks_ab.txt).
+//   R <= 3  RowSweep: a ring of 4 rows, FMAs row by row.  These kernels hold 60-80 VGPRs for 6-8 workgroups per CU; with
+//           every row live they take 68 / 76 / 84 and lose an occupancy step.
+template <int R>
+constexpr bool kRowsLiveB = R >= 4;
+constexpr int kRingB = 4;
 
-// The phases of one output tile once its window is in A (behind a barrier): pass A, [ghost columns], pass B
-// (parked in registers), the H^T y / x loads, O staging, row-major epilogue, [RelError partials].
-template <typename T, int R, bool EDGE, int D>
-__device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
-                                     const T* __restrict__ bs, T* __restrict__ xns, double* __restrict__ partials,
-                                     const T* __restrict__ xrs, const int tid) {
+template <typename T, int R, bool EDGE, typename Mark>
+__device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, const T* KT, const T* GH, int ty0, int tx0,
+                                     const T* __restrict__ bs, const T* __restrict__ xrs, T* __restrict__ xns,
+                                     bool want_part, double& part_d, double& part_x, int tid, Mark&& tmark) {
+  using L = Layout<T, R>;
+  using B = BlockB<T, R>;
+  constexpr int CA = L::CA, PTP = B::PTP;
+  const int n0 = p.n0, n1 = p.n1;
+  const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
+  int wv, ln;
+  wave_lane(tid, wv, ln);
+  int rpl, cil, wr0, wc0;
+  B::item(wv, ln, rpl, cil, wr0, wc0);
+  const int r0 = wr0 + 2 * rpl, c0 = wc0 + 4 * cil;  // the block's first pixel (tile-relative)
+  // interior tiles: wave-uniform base (the region's first pixel) + 32-bit lane offset (lane_ptr)
+  auto voff = [&](int q) { return (unsigned)((2 * rpl + q) * n1 + 4 * cil) * (unsigned)sizeof(T); };
+  auto load_rows = [&](const T* __restrict__ src, T(&v)[2][4]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int gr = ty0 + r0 + q, gc = tx0 + c0;
+      if (!EDGE) {
+        ld_vec<T, 4>(lane_ptr<const T>(src, ty0, tx0 + wc0, n1, wr0, voff(q)), v[q]);
+      } else if (vec_inside(p, gr, gc)) {  // edge tile, but this vector is inside: one 16-B load
+        ld_vec<T, 4>(src + (int64_t)gr * n1 + gc, v[q]);
+      } else {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) v[q][w] = (gr < n0 && gc + w < n1) ? src[(int64_t)gr * n1 + gc + w] : T(0);
+      }
+    }
+  };
+  T bv[2][4], xv[2][4];
+  auto load_epilogue = [&]() {
+    if (kProbes && (p.diag & 512)) {  // timing probe only (WRONG results): no H^T y loads
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int w = 0; w < 4; ++w) bv[q][w] = T(0);
+    } else {
+      load_rows(bs, bv);
+    }
+  };
+  T yc[2][4], tv[2][4], acc[4][2];  // acc[w][q]: column c0 + w, row r0 + q
+  if (kProbes && (p.diag & 64)) {   // timing probe only (WRONG results): no TV chain, no sweep
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int w = 0; w < 4; ++w) yc[q][w] = tv[q][w] = acc[w][q] = A[tid + q * 64 + w];
+    load_epilogue();
+    tmark(5);
+  } else {
+    const T* src = PT + (CA - 2 * R + c0) * PTP + r0;
+    if constexpr (kRowsLiveB<R>) {
+      tv_block<T, R, EDGE>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tmark(5);
+      load_epilogue();
+      sweep_w<T, R, 4, 2, PTP>(src, p.g1, acc);
+    } else {
+      T g1[4 * R + 1];  // the G1 taps in scalar registers before the first PT read
+#pragma unroll
+      for (int k = 0; k <= 4 * R; ++k) {
+        g1[k] = p.g1[k];
+        asm volatile("" : "+s"(g1[k]));
+      }
+      RowSweep<T, R, 4, 2, PTP, kRingB> sw;
+      tv_block<T, R, EDGE>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tmark(5);
+      load_epilogue();
+      sw.start(src);
+      sw.run(src, g1, acc);
+    }
+    if (edge_cols) ghost_fix_pre_w<T, R, 4, 2, TY>(tx0 + c0, n1, r0, GH, KT + kKT, acc);
+  }
+  // x (RelError partials only) behind the sweep: issued under a branch ahead of it, its registers would be copied, and
+  // so waited for, where the branches join
+  if (want_part) load_rows(xrs, xv);
+  tmark(6);
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    T g[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) g[w] = p.tv ? acc[w][q] + tv[q][w] : acc[w][q];
+    if (kProbes && (p.diag & 1024)) {  // timing probe only (WRONG results): no x_new stores
+      if (g[0] + yc[q][0] + bv[q][0] == T(-12345)) xns[0] = T(0);
+      continue;
+    }
+    T* vdst = EDGE ? nullptr : lane_ptr<T>(xns, ty0, tx0 + wc0, n1, wr0, voff(q));
+    finish_vec<T, EDGE>(p, ty0 + r0 + q, tx0 + c0, g, bv[q], yc[q], xv[q], xns, vdst, want_part, part_d, part_x);
+  }
+}
+
+// ---- pass B and the staged epilogue of the fp64 tile (Layout's 2 x 1 items): every thread parks its results in
+// registers, loads H^T y, stages them through O and the workgroup finishes the tile in row-major order.
+template <typename T, int R, bool EDGE, int D, typename Mark>
+__device__ inline void pass_b_staged(const PgdParams<T>& p, T* A, T* PT, const T* KT, const T* GH, int ty0, int tx0,
+                                     const T* __restrict__ bs, const T* __restrict__ xrs, T* __restrict__ xns,
+                                     bool want_part, double& part_d, double& part_x, int tid, Mark&& tmark) {
   using L = Layout<T, R>;
   using S = Stage<T, R>;
   constexpr int CW = L::CW;
   constexpr int V = L::V;
   constexpr int KB = cdiv(L::NPB, kThreads);
-  T* A = reinterpret_cast<T*>(smem);
-  T* PT = A + L::AR * L::AP;
-  T* KT = PT + L::AC * L::PTP;  // H taps for runtime-indexed reads (boundary corrections)
-  T* GH = reinterpret_cast<T*>(smem + kGhOff<T, R>);  // boundary-column ghost terms (edge-column tiles)
   const int n1 = p.n1;
-  const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
-  double part_d = 0.0, part_x = 0.0;
-  const bool want_part = partials != nullptr;
-  const bool tracing = kProbes && (p.diag & 32) != 0;
-  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kGhBytes<T, R>);
-  auto tmark = [&](int pt) {
-    if (tracing && (tid & 63) == 0) ts[(tid >> 6) * 8 + pt] = clock64();
-  };
-  tmark(2);
   const bool skip_passes = kProbes && (p.diag & 64) != 0;  // timing probe only (WRONG results)
-  if (!skip_passes) pass_a<T, R, EDGE, D>(p, A, PT, KT, ty0, tid);
-  tmark(3);
-  __syncthreads();
-  if (edge_cols) {
-    ghost_cols_coop<T, R>(p.k1, PT, GH, tx0, n1, tid);
-    __syncthreads();
-  }
-  tmark(4);
   T st[KB][V][CW];
   if (skip_passes) {
 #pragma unroll
@@ -763,12 +889,57 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
       finish_vec<T, EDGE>(p, ty0 + r, tx0 + V * cq, g, hb.v[s], y, hb.x[s], xns, vdst, want_part, part_d, part_x);
     }
   }
+}
+
+// Rows in flight per G sweep (tile2d.hpp sweep's D): 0 = compiler-scheduled (default); A/B builds limit it
+#ifndef PXA_PGD_SWEEP_DEPTH
+#define PXA_PGD_SWEEP_DEPTH 0
+#endif
+
+// The phases of one output tile once its window is in A (behind a barrier): pass A, [ghost columns], then fp32: pass B
+// and the epilogue on row-major blocks, no further barrier; fp64: pass B (parked in registers), the H^T y / x loads, O
+// staging, row-major epilogue; [RelError partials].
+template <typename T, int R, bool EDGE, int D>
+__device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
+                                     const T* __restrict__ bs, T* __restrict__ xns, double* __restrict__ partials,
+                                     const T* __restrict__ xrs, const int tid) {
+  using L = Layout<T, R>;
+  T* A = reinterpret_cast<T*>(smem);
+  T* PT = A + L::AR * L::AP;
+  T* KT = PT + L::AC * L::PTP;  // H taps for runtime-indexed reads (boundary corrections)
+  T* GH = reinterpret_cast<T*>(smem + kGhOff<T, R>);  // boundary-column ghost terms (edge-column tiles)
+  const int n1 = p.n1;
+  const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
+  double part_d = 0.0, part_x = 0.0;
+  const bool want_part = partials != nullptr;
+  const bool tracing = kProbes && (p.diag & 32) != 0;
+  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kGhBytes<T, R>);
+  auto tmark = [&](int pt) {
+    if (tracing && (tid & 63) == 0) ts[(tid >> 6) * 8 + pt] = clock64();
+  };
+  tmark(2);
+  const bool skip_passes = kProbes && (p.diag & 64) != 0;  // timing probe only (WRONG results)
+  if (!skip_passes) pass_a<T, R, EDGE, D>(p, A, PT, KT, ty0, tid);
+  tmark(3);
+  __syncthreads();
+  if (edge_cols) {
+    ghost_cols_coop<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, tx0, n1, tid);
+    __syncthreads();
+  }
+  tmark(4);
+  if constexpr (sizeof(T) == 4) {  // no barrier from here on: each thread finishes its own block
+    pass_b_blocks<T, R, EDGE>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
+  } else {
+    pass_b_staged<T, R, EDGE, D>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
+  }
   tmark(7);
   if (want_part) wave_partials(part_d, part_x, partials, tile * kPartWaves + (tid >> 6));
   const unsigned nb = gridDim.x, bid = blockIdx.x;
-  if (tracing && (bid == 0 || bid == 1 || bid == nb / 2 || bid == nb - 1)) {
+  // traced workgroups: 0 (a corner tile), 9 and grid/2 + 8 (at 2048^2 tiles (8, 1) and (4, 1): interior), grid-1 (a tile
+  // of the image's first column: boundary-column corrections in the sweep of the waves that hold columns 0 .. 31)
+  if (tracing && (bid == 0 || bid == 9 || bid == nb / 2 + 8 || bid == nb - 1)) {
     __syncthreads();
-    const int slot = bid == 0 ? 0 : bid == 1 ? 1 : bid == nb / 2 ? 2 : 3;
+    const int slot = bid == 0 ? 0 : bid == 9 ? 1 : bid == nb / 2 + 8 ? 2 : 3;
     if (tid < 32) g_tile_trace[slot * 32 + tid] = ts[tid];
   }
 }

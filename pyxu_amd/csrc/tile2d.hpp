@@ -206,8 +206,8 @@ __device__ inline void ghost_fix(int i0, int n, int q0, const T* __restrict__ sr
 // columns pg + m on each side (pg = -R, n) -- ghost_fix()'s gh with the same fma order.  With ghost_fix()
 // the few lanes owning columns within R of the border compute them all, one 2R+1-tap sum per ghost
 // column and lane: one wave then runs thousands of cycles past the others (measured by the PGD
-// kernels' s_memtime trace).  Followed by a barrier, then ghost_fix_pre() in pass B.
-template <typename T, int R>
+// kernels' s_memtime trace).  Followed by a barrier, then ghost_fix_pre() in pass B.  PTP: the pitch of PT.
+template <typename T, int R, int PTP = Layout<T, R>::PTP>
 __device__ inline void ghost_cols_coop(const T* __restrict__ k, const T* PT, T* GH, int tx0, int n, int lt = threadIdx.x,
                                        int nthr = kThreads) {
   using L = Layout<T, R>;
@@ -217,7 +217,7 @@ __device__ inline void ghost_cols_coop(const T* __restrict__ k, const T* PT, T* 
     T g = T(0);
     if (row - R >= 0 && row + R < L::AC) {  // else no output of this tile uses it
 #pragma unroll
-      for (int q = -R; q <= R; ++q) g = fma(k[q + R], PT[(row + q) * L::PTP + r], g);
+      for (int q = -R; q <= R; ++q) g = fma(k[q + R], PT[(row + q) * PTP + r], g);
     }
     GH[(side * R + m) * TY + r] = g;
   }
@@ -318,6 +318,155 @@ struct Stage {
     }
   }
 };
+
+// Row-major pass-B blocks of the fp32 PGD tile kernel: an item is RB = 2 tile rows x CB = 4 columns, i.e. two 16-B row
+// vectors of the tile, so the thread that sweeps G1 for them also loads H^T y, applies the prox and stores x_new from
+// its registers (no O staging).  The G1 sweep runs along the item's 4-column side: 4 outputs share every PT row, read
+// as one ds_read_b64 (the item's two tile rows).
+//   PT pitch PTP = TY + 4 (4 PTP = 16 mod 64 dwords): a 32-lane ds_read_b64 group of 4 column items x 8 row pairs reads
+//   dwords 16 ci + 2 rp + {0, 1} (+ const): 64 distinct banks; pass A's ds_write_b128 (8 lanes = 8 row groups of one PT
+//   row) stay 32 contiguous dwords.
+//   A wave is 8 column items x 8 row pairs = 16 tile rows x 32 columns: every global access of it covers whole 128-B
+//   lines.  The row pair of a lane is permuted within its 8 so that each 16-lane ds_read_b128 group ({0-3, 12-15,
+//   20-27}, ...) holds row pairs two apart: the yk reads of A (pitch AP = 28 mod 32, so 2 AP = -8 mod 64) are then four
+//   disjoint 16-dword runs.  All conflict-free under the MI355X_MICROARCH.md §LDS bank model (scripts/ldsbank.py).
+template <typename T, int R>
+struct BlockB {
+  using L = Layout<T, R>;
+  static constexpr int RB = 2, CB = 4;
+  static constexpr int PTP = TY + 4;
+  static constexpr int WR = 16, WC = 32;      // tile rows x columns of one wave
+  static constexpr int NRP = WR / RB, NCI = WC / CB;
+  static_assert(sizeof(T) == 4 && TY == 2 * WR && TX == 2 * WC && kThreads == 256, "four waves, 2 x 2 over the tile");
+  static_assert(PTP <= L::PTP, "PT keeps inside Layout's carve");
+  // (wave, lane) -> row pair rpl and column item cil within the wave's region, and the region's first row / column
+  __device__ static inline void item(int wv, int ln, int& rpl, int& cil, int& wr0, int& wc0) {
+    const int l = ln & 31, k = l >> 2;
+    rpl = k ^ (((k + 2) >> 2) & 1);  // 0 1 3 2 5 4 6 7
+    cil = 4 * (ln >> 5) + (l & 3);
+    wr0 = WR * (wv >> 1);
+    wc0 = WC * (wv & 1);
+  }
+};
+
+// sweep() with a W-element row vector (W a multiple of the packed width) and the ring in the caller's hands: start()
+// issues the first D row reads, run() issues row j + D and then consumes row j, D rows in flight, the order fixed by
+// scheduling barriers, so that the wait before the FMAs of a row counts the reads behind it (lgkmcnt(D)) instead of
+// draining them.  `g`: the taps, already in registers (a scalar load among the reads would turn every counted wait into
+// a drain).  Same FMAs in the same order per output as sweep(): same bits.
+template <typename T, int R, int NO, int W, int PS, int D>
+struct RowSweep {
+  using P = typename Pk<T>::type;
+  static constexpr int NP = W / Pk<T>::W;
+  static constexpr int NJ = NO + 4 * R;
+  static_assert(W % Pk<T>::W == 0 && D >= 1, "whole packed rows, a ring of at least one");
+  typedef T Row __attribute__((ext_vector_type(W)));
+  // (volatile: the compiler would pair the b64 reads of two PT rows into one ds_read2_b64, which the LDS serves at
+  // half the rate of two ds_read_b64 -- MI355X_MICROARCH.md §LDS; the LDS address space is named because a volatile
+  // access through a generic pointer stays a flat load)
+  __device__ static inline Row ld(const T* p) {
+    return *(const volatile __attribute__((address_space(3))) Row*)p;
+  }
+  Row ring[D];
+  __device__ inline void start(const T* __restrict__ src) {
+#pragma unroll
+    for (int j = 0; j < D && j < NJ; ++j) ring[j] = ld(src + j * PS);
+  }
+  __device__ inline void run(const T* __restrict__ src, const T (&g)[4 * R + 1], T (&out)[NO][W]) {
+    P acc[NO][NP];
+#pragma unroll
+    for (int o = 0; o < NO; ++o)
+#pragma unroll
+      for (int h = 0; h < NP; ++h) acc[o][h] = Pk<T>::splat(T(0));
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      P row[NP];
+      __builtin_memcpy(&row[0], &ring[j % D], sizeof(Row));
+      if (j + D < NJ) ring[j % D] = ld(src + (j + D) * PS);
+      __builtin_amdgcn_sched_barrier(0);  // the read stays ahead of row j's FMAs ...
+#pragma unroll
+      for (int o = 0; o < NO; ++o) {
+        const int k = j - o;
+        if (k >= 0 && k <= 4 * R) {
+          const P gg = Pk<T>::splat(g[k]);
+#pragma unroll
+          for (int h = 0; h < NP; ++h) acc[o][h] = gg * row[h] + acc[o][h];
+        }
+      }
+      // ... and those ahead of the next read: row by row, NO independent chains.  (The empty statement takes the
+      // accumulators through the ordered instruction chain: instruction selection would otherwise gather each
+      // output's FMAs, which the scheduling barriers do not order, into one dependent run behind all reads.)
+#pragma unroll
+      for (int o = 0; o < NO; ++o)
+#pragma unroll
+        for (int h = 0; h < NP; ++h) asm volatile("" : "+v"(acc[o][h]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int o = 0; o < NO; ++o) __builtin_memcpy(&out[o][0], &acc[o][0], sizeof(T) * W);
+  }
+};
+
+// sweep() with a W-element row vector, compiler-scheduled: every row read at once, then the FMAs.  The row reads are
+// volatile LDS accesses: as plain loads the compiler pairs the b64 reads of two PT rows into one ds_read2_b64, which the
+// LDS serves at half the rate of two ds_read_b64 (MI355X_MICROARCH.md §LDS; measured: 22.4-22.7 us per step paired
+// against 21.4-21.7 single, profiles/pgd_blocks_ab.txt); the LDS address space is named because a volatile access through
+// a generic pointer stays a flat load.  Same FMAs in the same order per output as sweep(): same bits.
+template <typename T, int R, int NO, int W, int PS>
+__device__ inline void sweep_w(const T* __restrict__ src, const T* __restrict__ g, T (&out)[NO][W]) {
+  using P = typename Pk<T>::type;
+  constexpr int NP = W / Pk<T>::W;
+  constexpr int NJ = NO + 4 * R;
+  typedef T Row __attribute__((ext_vector_type(W)));
+  P acc[NO][NP];
+#pragma unroll
+  for (int o = 0; o < NO; ++o)
+#pragma unroll
+    for (int h = 0; h < NP; ++h) acc[o][h] = Pk<T>::splat(T(0));
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const Row t = *(const volatile __attribute__((address_space(3))) Row*)(src + j * PS);
+    P row[NP];
+    __builtin_memcpy(&row[0], &t, sizeof(Row));
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const int k = j - o;
+      if (k >= 0 && k <= 4 * R) {
+        const P gg = Pk<T>::splat(g[k]);
+#pragma unroll
+        for (int h = 0; h < NP; ++h) acc[o][h] = gg * row[h] + acc[o][h];
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 0; o < NO; ++o) __builtin_memcpy(&out[o][0], &acc[o][0], sizeof(T) * W);
+}
+
+// ghost_fix_pre() for outputs that are W-vectors across the sweep axis
+template <typename T, int R, int NO, int W, int GP>
+__device__ inline void ghost_fix_pre_w(int i0, int n, int cc, const T* __restrict__ GH, const T* __restrict__ kt,
+                                       T (&acc)[NO][W]) {
+#pragma unroll
+  for (int side = 0; side < 2; ++side) {
+    const int pg = side == 0 ? -R : n;
+    const bool hit = side == 0 ? (i0 < R) : (i0 + NO - 1 >= n - R && i0 < n);
+    if (!hit) continue;
+#pragma unroll
+    for (int o = 0; o < NO; ++o) {
+      const int i = i0 + o;
+      if (i >= n || (side == 0 ? i >= R : i < n - R)) continue;
+#pragma unroll
+      for (int m = 0; m < R; ++m) {
+        const int t = i - (pg + m);
+        if (t < -R || t > R) continue;
+        const T kk = kt[t + R];
+        const auto* src = GH + (side * R + m) * GP + cc;
+#pragma unroll
+        for (int v = 0; v < W; ++v) acc[o][v] = fma(-kk, src[v], acc[o][v]);
+      }
+    }
+  }
+}
 
 // XCD-aware tile order (speed only): XCD group g = blockIdx % 8 owns a contiguous band of tiles.
 __device__ inline unsigned xcd_tile(unsigned bid, unsigned nb) {

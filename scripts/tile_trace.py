@@ -1,5 +1,5 @@
 """Development probe: phase durations of the tile kernel (pgd_tv2d_kernel) from its s_memtime trace
-(PXA_TUNE_PGD_DIAG bit 5): workgroups 0, 1, grid/2, grid-1.  usage: python scripts/tile_trace.py [n] [sigma]"""
+(PXA_TUNE_PGD_DIAG bit 5): workgroups 0 (corner tile), 9 and grid/2 + 8 (interior tiles at 2048^2), grid-1 (first-column tile).  usage: python scripts/tile_trace.py [n] [sigma]"""
 import ctypes as ct
 import sys
 
@@ -25,10 +25,12 @@ buf = np.zeros(128, dtype=np.uint64)
 assert lib.pxa_pgd_tile_trace(buf.ctypes.data_as(ct.c_void_p), 128) == 0
 for k, v in prev:
     _dev.tuning(k, v)
-names = ["load", "B1", "passA", "B2(+ghost)", "passB", "stage O+B", "epilogue"]
+# fp32 (row-major pass-B blocks, no staging): H^T y loads + first PT rows issued + TV chain, the G1 sweep, finish in
+# registers + x_new stores; fp64 would be pass B, H^T y loads + O staging, row-major epilogue (this probe runs fp32)
+names = ["load", "B1", "passA", "B2(+ghost)", "loads+TV", "sweep", "epilogue"]
 tr = buf.astype(np.int64).reshape(4, 4, 8)
 t0 = tr[:, :, 0].min()
-for slot, lab in enumerate(["wg0", "wg1", "wg n/2", "wg n-1"]):
+for slot, lab in enumerate(["wg0", "wg9", "wg n/2+8", "wg n-1"]):
     for w in range(4):
         d = np.diff(tr[slot, w])
         print(f"{lab:7s} w{w} start {tr[slot, w, 0] - t0:7d}  " + "  ".join(f"{names[i]} {d[i]:6d}" for i in range(7)),
