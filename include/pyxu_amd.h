@@ -14,7 +14,7 @@
  *       * pxa_pgd_tv2d_plan() allocates the plan's 4-byte device counter (released by
  *         pxa_pgd_tv2d_plan_free()); call it before a capture, then capture pxa_pgd_tv2d_plan_step();
  *       * pxa_host_alloc() / pxa_host_free() allocate / release coherent host memory (their purpose);
- *       * pxa_pds_kernel_ms() and pxa_pgd_tile_trace() (measurement hooks) wait for recorded events /
+ *       * pxa_pds_kernel_ms(), pxa_pgd_tile_trace() and pxa_pgd_tile_timeline() (measurement hooks) wait for recorded events /
  *         copy a device symbol to the host;
  *   - `stream` is a hipStream_t (NULL = legacy default stream); launches are asynchronous;
  *   - functions are re-entrant (safe from Pyxu's solver worker thread, reference
@@ -635,8 +635,14 @@ int pxa_pgd_tv2d_plan_step_wpub(void* plan, double a, double tau, double prox_w,
 int pxa_pgd_tv2d_plan_free(void* plan);
 int pxa_pgd_tv2d_last_kernel(void);
 /* Diagnostics: s_memtime stamps of the tile kernel's last launch under PXA_TUNE_PGD_DIAG bit 5
- * (workgroups 0, 9, grid/2 + 8, grid-1; waves 0..3; 8 phase points; n <= 128 words). */
+ * (workgroups 0, 9, grid/2 + 8, grid-1, 8; waves 0..3; 8 phase points; n <= 160 words). */
 int pxa_pgd_tile_trace(uint64_t* host_out, int n);
+/* Diagnostics (probe build only, else PXA_ERR_UNSUPPORTED): the launch timeline of the tile kernel's last launch under
+ * PXA_TUNE_PGD_DIAG bit 5: per workgroup, in blockIdx order, 3 words -- s_memtime at its start, at its end, and
+ * tile index | tile class << 32 (classes as pxa_pgd_tv2d_tile_classes) | XCC_ID << 36 | HW_ID[15:0] << 40 of the
+ * workgroup's first wave; nwg <= 16384 workgroups.  The counter's base differs between XCDs and between CUs.  Bit 11 of the same key (probe build) runs col and row tiles on
+ * the generic path. */
+int pxa_pgd_tile_timeline(uint64_t* host_out, int nwg);
 int pxa_pgd_tv2d_step(int dtype, int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0, const int32_t* off0,
                       const double* coef0, int nt1, const int32_t* off1, const double* coef1, double h0, double h1,
                       double lam, double mu, double a, double tau, int prox, double prox_w, const void* x,
@@ -851,6 +857,18 @@ int pxa_pds_step_la(int dtype, int algo, const int64_t* geom, const int32_t* nta
                     const double* coefs, const double* diff, const double* scal, int prox, int h_kind, int primed,
                     void* x, const void* u, const void* z, const void* hty, void* x_out, void* u_out, void* z_out,
                     void* work_q, void* work_kt, void* work_w, int nseg, void* stream);
+
+/* Census of the tile classes the fp32 fused PGD tile kernel (pxa_pgd_tv2d_step and the plan forms) dispatches for
+ * `stack` images of n0 x n1 pixels and blur reach R (1 .. 8): counts[0 .. 3] = interior, col, row, generic tiles.
+ *   interior: the tile's whole window (2R rows, the 2R columns rounded up to 16-B vectors) lies inside the image;
+ *   col:      the window's rows lie inside, the tile's own columns end exactly on one border of the image and the
+ *             other side's halo is inside;
+ *   row:      the mirror image (own rows end exactly on the top or the bottom border);
+ *   generic:  every other tile (corners, ragged last tiles, a halo that only grazes a border, images one tile wide or
+ *             high), and every tile when `aligned` is 0 (some pointer off a 16-B boundary) or n1 is no multiple of 4.
+ * The fp64 kernel runs col and row tiles on its generic path: for fp64 read counts[1] + counts[2] + counts[3] as
+ * generic.  Host only: no GPU is touched.  Returns PXA_OK or PXA_ERR_ARG. */
+int pxa_pgd_tv2d_tile_classes(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts);
 
 #ifdef __cplusplus
 }

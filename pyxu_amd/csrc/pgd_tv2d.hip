@@ -34,6 +34,10 @@
 // LDS pitches / lane orders are conflict-free for R = 6 fp32 under the MI355X_MICROARCH.md §LDS
 // bank model (scripts/ldsbank.py, scripts/ldsbank_blocks.py).  The blockIdx -> tile map is XCD-aware: each of the
 // 8 XCDs owns a contiguous band of tiles so that halo re-reads of x / x_prev hit its own L2.
+// Tile classes (tile2d.hpp tile_class; fp32): a tile whose window lies inside the image is `interior` (no bounds tests);
+// one that ends exactly on one border of an aligned image is `col` or `row` and runs the interior code on its interior
+// axis, skipping the halo beyond the border and correcting the R boundary rows / columns of G from ghost terms with
+// compile-time tap indices; every other tile is `generic` (bounds tests, runtime-indexed corrections).
 #include "tile2d.hpp"
 #include <type_traits>
 
@@ -109,10 +113,18 @@ struct PgdParams {
 // saves; it was removed.
 
 // Timing trace (PXA_TUNE_PGD_DIAG bit 5, read by pxa_pgd_tile_trace): s_memtime stamps of waves 0-3 of
-// workgroups 0, 9, grid/2 + 8 and grid-1, 8 points of their tile.  Staged in LDS beyond the kernel's own
+// workgroups 0, 9, grid/2 + 8, grid-1 and 8, 8 points of their tile.  Staged in LDS beyond the kernel's own
 // carve, dumped at exit.
-constexpr int kTraceWords = 4 * 4 * 8;
+constexpr int kTraceWords = 5 * 4 * 8;
 __device__ unsigned long long g_tile_trace[kTraceWords];
+// Launch timeline (the same bit, read by pxa_pgd_tile_timeline; probe build only): start stamp, end stamp and
+// tile | class << 32 | XCC_ID << 36 | HW_ID[15:0] << 40 of every workgroup, in blockIdx order.  The counter's
+// base differs between XCDs and, as measured, between CUs: scripts/tile_trace.py takes stamps relative to the first
+// start on the same CU.
+#if PXA_PROBES
+constexpr unsigned kTimelineWgs = 1u << 14;
+__device__ unsigned long long g_tile_timeline[3 * kTimelineWgs];
+#endif
 
 // Every multiply-add outside the Toeplitz sweeps is written as an explicit fma (the TV stencil's
 // two-product sums as fma(a, b, c * d)): under fp-contract=fast the compiler fuses or not, and picks
@@ -236,8 +248,7 @@ __device__ inline void wave_lane(int lt, int& wv, int& ln) {
 // Interior tiles: the address of a vector as a wave-uniform 64-bit base -- element (row0 + ru, col0) of the image,
 // formed in scalar registers -- plus a zero-extended 32-bit byte offset per lane (the saddr + voffset form of the
 // global loads / stores: no 64-bit address arithmetic in the vector unit).  The kernels' `interior` predicate bounds
-// n1 so that the lane offsets, at most (AR n1 + AC) sizeof(T), fit in 32 bits.
-constexpr int kMaxInteriorN1 = 1 << 22;  // (64 rows x 2^22 columns x 8 B = 2^31)
+// n1 (tile2d.hpp kMaxInteriorN1) so that the lane offsets, at most (AR n1 + AC) sizeof(T), fit in 32 bits.
 template <typename T>
 __device__ inline T* lane_ptr(T* img, int row0, int col0, int n1, int ru, unsigned voff) {
   T* base = img + ((int64_t)row0 * n1 + col0) + ru * n1;  // (ru n1 < 2^28: |ru| <= 64, n1 <= kMaxInteriorN1)
@@ -245,21 +256,42 @@ __device__ inline T* lane_ptr(T* img, int row0, int col0, int n1, int ru, unsign
   return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + (size_t)voff);
 }
 
-template <typename T, int R, bool EDGE>
+// The side of a col / row tile (tile2d.hpp tile_class): 0 when it holds the image's first columns / rows, 1 its last.
+template <int C>
+__device__ inline int tile_side(int ty0, int tx0) {
+  return __builtin_amdgcn_readfirstlane(C == kTileCol ? (tx0 == 0 ? 0 : 1) : (ty0 == 0 ? 0 : 1));
+}
+
+// `C`: the tile's class.  Col and row tiles load as interior ones do, except that the halo vectors beyond their one
+// border -- the CV side vectors of every window row / the 2R rows of one vertical block, side vectors included --
+// are not loaded and stay zero; the own items (and so the window partials) are never among them.
+template <typename T, int R, int C>
 __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const T* __restrict__ xs,
                                  const T* __restrict__ xps, Window<T, R>& w, int lt) {
   using L = Layout<T, R>;
   using W = Window<T, R>;
   constexpr int V = L::V;
   constexpr int CA = L::CA;
+  constexpr bool EDGE = C == kTileGeneric;
   const int n0 = p.n0, n1 = p.n1;
   int wv, ln;
   wave_lane(lt, wv, ln);
+  const int side = tile_side<C>(ty0, tx0);
 #pragma unroll
   for (int k = 0; k < W::K0; ++k) {
     int rl, gl, ru, gu;
     if (W::item(k, wv, ln, rl, gl, ru, gu)) {
       if (!EDGE) {
+        if ((C == kTileCol || C == kTileRow) && k >= W::KI) {
+          const int r = rl + ru, g = gl + gu;
+          const bool outside = C == kTileCol ? (side == 0 ? g < W::CV : g >= W::CV + W::TV)
+                                             : (side == 0 ? r < 2 * R : r >= 2 * R + TY);
+          if (outside) {
+#pragma unroll
+            for (int v = 0; v < V; ++v) w.xv[k][v] = w.pv[k][v] = T(0);
+            continue;
+          }
+        }
         const unsigned voff = (unsigned)(rl * n1 + V * gl) * (unsigned)sizeof(T);
         ld_vec<T, V>(lane_ptr<const T>(xs, ty0 - 2 * R, tx0 - CA + V * gu, n1, ru, voff), w.xv[k]);
         if (kProbes && (p.diag & 256)) {  // timing probe only (WRONG results): one window array instead of two
@@ -313,11 +345,47 @@ __host__ __device__ constexpr int pt_pitch() {
 }
 
 // ---- pass A: PT[col][row] = (G0 yk)[row][col] for the TY tile rows and all A columns
-template <typename T, int R, bool EDGE, int D = 0>
-__device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T* KT, int ty0, int tid = threadIdx.x) {
+// Bytes of the ghost-term region of the PGD tile kernel: the boundary-column terms of a col or generic tile (tile2d.hpp
+// kGhBytes) or the boundary-row terms of a row tile (fp32: R rows of AC columns); a tile has one or the other.
+template <typename T, int R>
+constexpr size_t kPgdGhBytes =
+    sizeof(T) == 4 && (size_t)R * Layout<T, R>::AC * sizeof(T) > kGhBytes<T, R> ? (size_t)R * Layout<T, R>::AC * sizeof(T)
+                                                                                  : kGhBytes<T, R>;
+
+// Row tiles: the R ghost rows of H0 yk beyond the tile's border (ghost_fix()'s gh, the same fma order: s ascending),
+// computed once per column group instead of once per item that needs them.  The NA items of a column group are NA
+// consecutive lanes of one wave: lane a < R evaluates ghost row m = a over the group's V columns and parks it in
+// GH[group][m][V]; the items within R rows of the border read all R back (pass_a).  Within one wave LDS accesses execute
+// in order, so no barrier stands between the stores and those reads.
+template <typename T, int R>
+__device__ inline void ghost_rows_coop(const PgdParams<T>& p, const T* A, T* GH, int side, int a, int b) {
+  using L = Layout<T, R>;
+  constexpr int V = L::V;
+  static_assert(R <= L::NA, "one ghost row per lane of a column group");
+  if (a < R) {
+    const T* src = A + ((side == 0 ? 0 : TY + R) + a) * L::AP + V * b;  // window row of ghost row a's first tap
+    T gh[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) gh[v] = T(0);
+#pragma unroll
+    for (int s = 0; s <= 2 * R; ++s) {
+      T w[V];
+      ld_vec<T, V>(src + s * L::AP, w);
+#pragma unroll
+      for (int v = 0; v < V; ++v) gh[v] = fma(p.k0[s], w[v], gh[v]);
+    }
+    st_vec<T, V>(GH + (b * R + a) * V, gh);
+  }
+}
+
+// `C`: the tile's class.  Col tiles run the interior stream (their rows are interior); row tiles correct the items
+// within R rows of their border from the ghost rows of ghost_rows_coop, tap indices known at compile time per row group.
+template <typename T, int R, int C, int D = 0>
+__device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T* KT, T* GH, int ty0, int tid = threadIdx.x) {
   using L = Layout<T, R>;
   constexpr int V = L::V;
   constexpr int KA = cdiv(L::NPA, kThreads);
+  constexpr bool EDGE = C == kTileGeneric;
   // one item per thread (fp32), in thread order: the 176 items of R = 6 fill waves 0, 1 and three quarters of wave 2; wave 3
   // has none.  Spreading them over four waves would issue four wave-passes instead of three for the same work.
   const bool edge_rows = EDGE && (ty0 < R || ty0 + TY > p.n0 - R);
@@ -327,7 +395,25 @@ __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T*
     if (it < L::NPA) {
       const int a = it % L::NA, b = it / L::NA;  // row group fastest (conflict-free reads/writes)
       T acc[V][V];
-      sweep<T, R, V, L::AP, D>(A + (V * a) * L::AP + V * b, p.g0, acc);
+      if constexpr (C == kTileRow) {
+        static_assert(KA == 1 && L::NPA % L::NA == 0 && 64 % L::NA == 0, "a column group is NA lanes of one wave");
+        static_assert(V == 4 && L::NA == 8 && R <= 8, "the row groups within R of a border: two on each side");
+        const int side = tile_side<C>(ty0, 0);
+        ghost_rows_coop<T, R>(p, A, GH, side, a, b);
+        sweep<T, R, V, L::AP, D>(A + (V * a) * L::AP + V * b, p.g0, acc);
+        __builtin_amdgcn_wave_barrier();
+        asm volatile("" ::: "memory");  // the compiler keeps the reads below behind the group's stores
+        const T* gh = GH + b * R * V;
+        if (side == 0) {
+          if (a == 0) ghost_sub<T, R, V, V, V, false, 0>(p.k0, gh, acc);
+          if (R > V && a == 1) ghost_sub<T, R, V, V, V, false, V>(p.k0, gh, acc);
+        } else {
+          if (a == L::NA - 1) ghost_sub<T, R, V, V, V, true, V - 1>(p.k0, gh, acc);
+          if (R > V && a == L::NA - 2) ghost_sub<T, R, V, V, V, true, 2 * V - 1>(p.k0, gh, acc);
+        }
+      } else {
+        sweep<T, R, V, L::AP, D>(A + (V * a) * L::AP + V * b, p.g0, acc);
+      }
       if (edge_rows) ghost_fix<T, R, V, L::AP>(ty0 + V * a, p.n0, ty0 - 2 * R, A + V * b, p.k0, KT, acc);
 #pragma unroll
       for (int v = 0; v < V; ++v) {
@@ -357,23 +443,29 @@ constexpr int kTvxP0 = 40;
 template <typename T, int R>
 constexpr int kTvxFloats = 9 * kTvxP0 + 9 * BlockB<T, R>::WR;
 
-template <typename T, int R, bool EDGE>
+// `C`: the tile's class.  Generic tiles test every q's pixel against the image; in a col or row tile the only pixels
+// outside are the column left of a first-column tile and the row above a top-row tile (q of the last column / row is
+// evaluated from the zeros beyond it, as everywhere), so only those halo evaluations are zeroed (`zq`).
+template <typename T, int R, int C>
 __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, int wv, int ln, T (&yc)[2][4],
                                 T (&tv)[2][4]) {
   using L = Layout<T, R>;
   using B = BlockB<T, R>;
   constexpr int CA = L::CA, AP = L::AP;
+  constexpr bool EDGE = C == kTileGeneric;
+  const bool first = (C == kTileCol || C == kTileRow) && tile_side<C>(ty0, tx0) == 0;
   constexpr bool kExchange = (2 * R - 1) * AP >= 2 * kTvxFloats<T, R>;
   const int n0 = p.n0, n1 = p.n1;
   int rpl, cil, wr0, wc0;
   B::item(wv, ln, rpl, cil, wr0, wc0);
   const int r0 = wr0 + 2 * rpl, c0 = wc0 + 4 * cil;  // the block's first pixel (tile-relative)
   const T* own = A + (r0 + 2 * R) * AP + CA + c0;
-  auto qat = [&](T yc_, T ydn, T yrt, int gr, int gc, T& q0, T& q1) {
+  auto qat = [&](T yc_, T ydn, T yrt, int gr, int gc, T& q0, T& q1, bool zq = false) {
     const T v0 = fma(p.g0a, yc_, p.g0b * ydn);
     const T v1 = fma(p.g1a, yc_, p.g1b * yrt);
     T w = tv_weight<T>(fma(v0, v0, v1 * v1), p.lam, p.mu, p.inv_mu);
     if (EDGE && !(gr >= 0 && gr < n0 && gc >= 0 && gc < n1)) w = T(0);
+    if (zq) w = T(0);
     q0 = v0 * w;
     q1 = v1 * w;
   };
@@ -412,12 +504,12 @@ __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, i
       if (ln < 32) {  // q0 of the row above the region
         const int tc = wc0 + ln;
         const T* h = A + (wr0 - 1 + 2 * R) * AP + CA + tc;
-        qat(h[0], h[AP], h[1], ty0 + wr0 - 1, tx0 + tc, hq0, hq1);
+        qat(h[0], h[AP], h[1], ty0 + wr0 - 1, tx0 + tc, hq0, hq1, C == kTileRow && first && wr0 == 0);
         E0[ln] = hq0;
       } else {  // q1 of the column left of the region
         const int j = ln - 32, tc = wc0 - 1;
         const T* h = A + (wr0 + j + 2 * R) * AP + CA + tc;
-        qat(h[0], h[AP], h[1], ty0 + wr0 + j, tx0 + tc, hq0, hq1);
+        qat(h[0], h[AP], h[1], ty0 + wr0 + j, tx0 + tc, hq0, hq1, C == kTileCol && first && wc0 == 0);
         E1[j] = hq1;
       }
     }
@@ -453,7 +545,9 @@ __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, i
     // q at window row r, columns c0 - 1 .. c0 + 3, from yk rows r (yr) and r + 1 (yn)
     auto qrow = [&](int r, const T(&yr)[6], const T(&yn)[6], T(&q0)[5], T(&q1)[5]) {
 #pragma unroll
-      for (int c = 0; c < 5; ++c) qat(yr[c], yn[c], yr[c + 1], ty0 + r0 - 1 + r, tx0 + c0 - 1 + c, q0[c], q1[c]);
+      for (int c = 0; c < 5; ++c)
+        qat(yr[c], yn[c], yr[c + 1], ty0 + r0 - 1 + r, tx0 + c0 - 1 + c, q0[c], q1[c],
+            first && (C == kTileCol ? c == 0 && c0 == 0 : r == 0 && r0 == 0));
     };
     T yr[6], yn[6];
     yrow(0, yr);
@@ -709,13 +803,14 @@ template <int R>
 constexpr bool kRowsLiveB = R >= 4;
 constexpr int kRingB = 4;
 
-template <typename T, int R, bool EDGE, typename Mark>
+template <typename T, int R, int C, typename Mark>
 __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, const T* KT, const T* GH, int ty0, int tx0,
                                      const T* __restrict__ bs, const T* __restrict__ xrs, T* __restrict__ xns,
                                      bool want_part, double& part_d, double& part_x, int tid, Mark&& tmark) {
   using L = Layout<T, R>;
   using B = BlockB<T, R>;
   constexpr int CA = L::CA, PTP = B::PTP;
+  constexpr bool EDGE = C == kTileGeneric;  // (col and row tiles: every own vector is inside, the interior's lane_ptr form)
   const int n0 = p.n0, n1 = p.n1;
   const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
   int wv, ln;
@@ -761,7 +856,7 @@ __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, c
   } else {
     const T* src = PT + (CA - 2 * R + c0) * PTP + r0;
     if constexpr (kRowsLiveB<R>) {
-      tv_block<T, R, EDGE>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv);
       tmark(5);
       load_epilogue();
       sweep_w<T, R, 4, 2, PTP>(src, p.g1, acc);
@@ -773,13 +868,25 @@ __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, c
         asm volatile("" : "+s"(g1[k]));
       }
       RowSweep<T, R, 4, 2, PTP, kRingB> sw;
-      tv_block<T, R, EDGE>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv);
       tmark(5);
       load_epilogue();
       sw.start(src);
       sw.run(src, g1, acc);
     }
     if (edge_cols) ghost_fix_pre_w<T, R, 4, 2, TY>(tx0 + c0, n1, r0, GH, KT + kKT, acc);
+    if constexpr (C == kTileCol) {
+      // ghost_fix_pre_w specialised on the side and on the block's column: only the blocks that hold a column within
+      // R of the border do anything, with constant tap indices (p.k1) and GH offsets
+      static_assert(R <= 8, "columns within R of a border: two blocks on each side");
+      if (tile_side<C>(ty0, tx0) == 0) {
+        if (c0 == 0) ghost_sub<T, R, 4, 2, TY, false, 0>(p.k1, GH + r0, acc);
+        if (R > 4 && c0 == 4) ghost_sub<T, R, 4, 2, TY, false, 4>(p.k1, GH + r0, acc);
+      } else {
+        if (c0 == TX - 4) ghost_sub<T, R, 4, 2, TY, true, 3>(p.k1, GH + R * TY + r0, acc);
+        if (R > 4 && c0 == TX - 8) ghost_sub<T, R, 4, 2, TY, true, 7>(p.k1, GH + R * TY + r0, acc);
+      }
+    }
   }
   // x (RelError partials only) behind the sweep: issued under a branch ahead of it, its registers would be copied, and
   // so waited for, where the branches join
@@ -899,7 +1006,7 @@ __device__ inline void pass_b_staged(const PgdParams<T>& p, T* A, T* PT, const T
 // The phases of one output tile once its window is in A (behind a barrier): pass A, [ghost columns], then fp32: pass B
 // and the epilogue on row-major blocks, no further barrier; fp64: pass B (parked in registers), the H^T y / x loads, O
 // staging, row-major epilogue; [RelError partials].
-template <typename T, int R, bool EDGE, int D>
+template <typename T, int R, int C, int D>
 __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
                                      const T* __restrict__ bs, T* __restrict__ xns, double* __restrict__ partials,
                                      const T* __restrict__ xrs, const int tid) {
@@ -908,27 +1015,32 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
   T* PT = A + L::AR * L::AP;
   T* KT = PT + L::AC * L::PTP;  // H taps for runtime-indexed reads (boundary corrections)
   T* GH = reinterpret_cast<T*>(smem + kGhOff<T, R>);  // boundary-column ghost terms (edge-column tiles)
+  constexpr bool EDGE = C == kTileGeneric;
   const int n1 = p.n1;
   const bool edge_cols = EDGE && (tx0 < R || tx0 + TX > n1 - R);
   double part_d = 0.0, part_x = 0.0;
   const bool want_part = partials != nullptr;
   const bool tracing = kProbes && (p.diag & 32) != 0;
-  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kGhBytes<T, R>);
+  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kPgdGhBytes<T, R>);
   auto tmark = [&](int pt) {
     if (tracing && (tid & 63) == 0) ts[(tid >> 6) * 8 + pt] = clock64();
   };
   tmark(2);
   const bool skip_passes = kProbes && (p.diag & 64) != 0;  // timing probe only (WRONG results)
-  if (!skip_passes) pass_a<T, R, EDGE, D>(p, A, PT, KT, ty0, tid);
+  if (!skip_passes) pass_a<T, R, C, D>(p, A, PT, KT, GH, ty0, tid);
   tmark(3);
   __syncthreads();
   if (edge_cols) {
     ghost_cols_coop<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, tx0, n1, tid);
     __syncthreads();
   }
+  if constexpr (C == kTileCol) {  // the one side that exists
+    ghost_cols_side<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, tile_side<C>(ty0, tx0), tid);
+    __syncthreads();
+  }
   tmark(4);
   if constexpr (sizeof(T) == 4) {  // no barrier from here on: each thread finishes its own block
-    pass_b_blocks<T, R, EDGE>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
+    pass_b_blocks<T, R, C>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
   } else {
     pass_b_staged<T, R, EDGE, D>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
   }
@@ -936,10 +1048,11 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
   if (want_part) wave_partials(part_d, part_x, partials, tile * kPartWaves + (tid >> 6));
   const unsigned nb = gridDim.x, bid = blockIdx.x;
   // traced workgroups: 0 (a corner tile), 9 and grid/2 + 8 (at 2048^2 tiles (8, 1) and (4, 1): interior), grid-1 (a tile
-  // of the image's first column: boundary-column corrections in the sweep of the waves that hold columns 0 .. 31)
-  if (tracing && (bid == 0 || bid == 9 || bid == nb / 2 + 8 || bid == nb - 1)) {
+  // of the image's first column: boundary-column corrections in the sweep of the waves that hold columns 0 .. 31),
+  // 8 (at 2048^2 tile (0, 1): a top-row tile)
+  if (tracing && (bid == 0 || bid == 9 || bid == nb / 2 + 8 || bid == nb - 1 || bid == 8)) {
     __syncthreads();
-    const int slot = bid == 0 ? 0 : bid == 9 ? 1 : bid == nb / 2 + 8 ? 2 : 3;
+    const int slot = bid == 0 ? 0 : bid == 9 ? 1 : bid == nb / 2 + 8 ? 2 : bid == nb - 1 ? 3 : 4;
     if (tid < 32) g_tile_trace[slot * 32 + tid] = ts[tid];
   }
 }
@@ -972,7 +1085,7 @@ __device__ inline void win_partials(const Window<T, R>& w, double* __restrict__ 
 }
 
 // One output tile of the tile kernel: phase 0 (window) into A, then the body.
-template <typename T, int R, bool EDGE>
+template <typename T, int R, int C>
 __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
                                 const T* __restrict__ xs, const T* __restrict__ xps, const T* __restrict__ bs,
                                 T* __restrict__ xns, double* __restrict__ partials, const T* __restrict__ xrs) {
@@ -980,12 +1093,13 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
   T* A = reinterpret_cast<T*>(smem);
   T* KT = A + L::AR * L::AP + L::AC * L::PTP;
   const int tid = threadIdx.x;
+  constexpr bool EDGE = C == kTileGeneric;
   if (EDGE && tid < 2 * R + 1) {
     KT[tid] = p.k0[tid];
     KT[kKT + tid] = p.k1[tid];
   }
   const bool tracing = kProbes && (p.diag & 32) != 0;
-  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kGhBytes<T, R>);
+  unsigned long long* ts = reinterpret_cast<unsigned long long*>(smem + kGhOff<T, R> + kPgdGhBytes<T, R>);
   auto tmark = [&](int pt) {
     if (tracing && (tid & 63) == 0) ts[(tid >> 6) * 8 + pt] = clock64();
   };
@@ -997,7 +1111,7 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
     for (int i = tid; i < L::AR * L::AP; i += kThreads) A[i] = T(0);
   } else {
     Window<T, R> w;
-    win_issue<T, R, EDGE>(p, ty0, tx0, xs, xps, w, tid);
+    win_issue<T, R, C>(p, ty0, tx0, xs, xps, w, tid);
     win_store<T, R>(p, A, w, tid);
     if (p.win_part && partials != nullptr) win_partials<T, R>(w, partials, tile, tid);
   }
@@ -1012,7 +1126,7 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
   // static VALU and changes nothing at R <= 6.
   int btid = tid;
   if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(btid));
-  pgd_tile_body<T, R, EDGE, PXA_PGD_SWEEP_DEPTH>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
+  pgd_tile_body<T, R, C, PXA_PGD_SWEEP_DEPTH>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
                                                  btid);
 }
 
@@ -1089,6 +1203,8 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
     return;
   }
   const unsigned vb = blockIdx.x - pub;
+  const bool timeline = kProbes && (p.diag & 32) != 0;
+  [[maybe_unused]] const unsigned long long tl0 = timeline ? clock64() : 0ull;
   extern __shared__ __align__(16) unsigned char smem_raw[];
   unsigned tile = xcd_tile(vb, p.ntiles);
   {  // the last XCD band walks backwards: an image's bottom-edge tiles (slower: boundary corrections)
@@ -1113,12 +1229,45 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
   // interior: the whole A window lies inside the image (so no boundary rows / columns of G either),
   // rows are 16-B aligned and a lane's 32-bit byte offset from the tile's window origin suffices (lane_ptr:
   // at most (AR n1 + AC) sizeof(T) < 2^32 for n1 <= kMaxInteriorN1) -> no bounds tests
-  const bool interior = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 &&
-                        tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;
-  if (interior)
-    pgd_tile<T, R, false>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
-  else
-    pgd_tile<T, R, true>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+  // col / row (fp32): the border cuts the window on one side only, along whole vectors / rows: the interior code on the
+  // axis that is interior, the skipped halo and the boundary terms of G on the other (tile2d.hpp tile_class).  fp64 runs
+  // them as generic tiles.
+  [[maybe_unused]] int tl_cls = kTileGeneric;
+  if constexpr (sizeof(T) == 4) {
+    int cls = __builtin_amdgcn_readfirstlane(tile_class(p.n0, p.n1, ty0, tx0, R, L::CA, p.vec_ok));
+    // measurement probe only: col and row tiles on the generic path, as before the classes existed
+    if (kProbes && (p.diag & 2048) && cls != kTileInterior) cls = kTileGeneric;
+    if (kProbes) tl_cls = cls;
+    if (cls == kTileInterior)
+      pgd_tile<T, R, kTileInterior>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+    else if (cls == kTileCol)
+      pgd_tile<T, R, kTileCol>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+    else if (cls == kTileRow)
+      pgd_tile<T, R, kTileRow>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+    else
+      pgd_tile<T, R, kTileGeneric>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+  } else {
+    const bool interior = p.vec_ok && img <= 0x7fffffff && p.n1 <= kMaxInteriorN1 && ty0 - 2 * R >= 0 && ty0 + TY + 2 * R <= p.n0 &&
+                          tx0 - L::CA >= 0 && tx0 + TX + L::CA <= p.n1;  // (tile_class() == kTileInterior)
+    if (kProbes && interior) tl_cls = kTileInterior;
+    if (interior)
+      pgd_tile<T, R, kTileInterior>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+    else
+      pgd_tile<T, R, kTileGeneric>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+  }
+#if PXA_PROBES
+  if (timeline) {
+    __syncthreads();
+    if (threadIdx.x == 0 && vb < kTimelineWgs) {
+      g_tile_timeline[3 * vb] = tl0;
+      g_tile_timeline[3 * vb + 1] = clock64();
+      // XCC_ID (hwreg 20, bits 3:0) and HW_ID (hwreg 4, bits 15:0: wave, SIMD, pipe, CU, SH, SE) of this wave
+      const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20), hw = __builtin_amdgcn_s_getreg((15 << 11) | 4);
+      g_tile_timeline[3 * vb + 2] = (unsigned long long)tile | (unsigned long long)tl_cls << 32 |
+                                    (unsigned long long)(xcc & 15u) << 36 | (unsigned long long)(hw & 0xffffu) << 40;
+    }
+  }
+#endif
   if (p.fold_vals != nullptr) tail_fold<T>(p, partials);
 }
 
@@ -1129,12 +1278,14 @@ int launch_pgd(const PgdParams<T>& p, const void* x, const void* xp, const void*
                hipStream_t s) {
   g_last_pgd_kernel = 1;
   // Layout + the ghost terms (+ the timing trace under PXA_TUNE_PGD_DIAG bit 5)
-  const size_t smem = kGhOff<T, R> + kGhBytes<T, R> + ((p.diag & 32) ? 256 : 0);
+  constexpr size_t kLds = 160 * 1024;  // per CU: the row tiles' ghost rows cost no resident workgroup
+  static_assert(kLds / (kGhOff<T, R> + kPgdGhBytes<T, R>) == kLds / (kGhOff<T, R> + kGhBytes<T, R>), "LDS occupancy step lost");
+  const size_t smem = kGhOff<T, R> + kPgdGhBytes<T, R> + ((p.diag & 32) ? 256 : 0);
   auto kern = pgd_tv2d_kernel<T, R>;
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)(kGhOff<T, R> + kGhBytes<T, R> + 256));
+                              (int)(kGhOff<T, R> + kPgdGhBytes<T, R> + 256));
     attr_set = true;
   }
   hipLaunchKernelGGL(kern, dim3(p.ntiles + (p.pub_src != nullptr ? 1u : 0u)), dim3(kThreads), smem, s, p, (const T*)x,
@@ -1267,9 +1418,33 @@ int pxa_pgd_tile_trace(uint64_t* host_out, int n) {
   return PXA_OK;
 }
 
+int pxa_pgd_tile_timeline(uint64_t* host_out, int nwg) {
+#if PXA_PROBES
+  if (!host_out || nwg < 0 || (unsigned)nwg > kTimelineWgs) return PXA_ERR_ARG;
+  if (hipMemcpyFromSymbol(host_out, HIP_SYMBOL(g_tile_timeline), (size_t)nwg * 24, 0, hipMemcpyDeviceToHost) != hipSuccess)
+    return PXA_ERR_UNSUPPORTED;
+  return PXA_OK;
+#else
+  (void)host_out, (void)nwg;
+  return PXA_ERR_UNSUPPORTED;  // the timeline exists only in the probe build
+#endif
+}
+
 int pxa_pgd_tv2d_partials_count(int64_t stack, int64_t n0, int64_t n1) {
   int64_t t = stack * ((n0 + TY - 1) / TY) * ((n1 + TX - 1) / TX) * kPartWaves;
   return (int)t;
+}
+
+int pxa_pgd_tv2d_tile_classes(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts) {
+  PXA_CHECK_ARG(counts != nullptr && stack >= 1 && n0 >= 1 && n1 >= 1 && n0 <= 0x7fffffff && n1 <= 0x7fffffff);
+  PXA_CHECK_ARG(R >= 1 && R <= kMaxR);
+  // the fp32 kernel's dispatch: 4-element vectors, the column halo of Layout<float, R>
+  constexpr int V = kVecN<float>;
+  const bool vec_ok = aligned != 0 && n1 % V == 0;
+  for (int c = 0; c < 4; ++c) counts[c] = 0;
+  for (int64_t ty0 = 0; ty0 < n0; ty0 += TY)
+    for (int64_t tx0 = 0; tx0 < n1; tx0 += TX) counts[tile_class((int)n0, (int)n1, (int)ty0, (int)tx0, R, rup(2 * R, V), vec_ok)] += stack;
+  return PXA_OK;
 }
 
 int pxa_pgd_tv2d_plan(int dtype, int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0, const int32_t* off0,

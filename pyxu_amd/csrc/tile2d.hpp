@@ -468,6 +468,69 @@ __device__ inline void ghost_fix_pre_w(int i0, int n, int cc, const T* __restric
   }
 }
 
+// ---- tile classes of the PGD tile kernel.  A tile whose window touches the image border in exactly one way, on an
+// aligned image, takes the interior code wherever its axis is interior:
+//   interior  the whole A window (2R rows, CA columns around the tile) lies inside the image
+//   col       the window's rows lie inside, the tile's own columns end exactly on one border (tx0 == 0 or tx0 + TX == n1)
+//             and the other side's CA halo is inside
+//   row       the mirror image: columns interior, ty0 == 0 or ty0 + TY == n0, the other side's 2R rows inside
+//   generic   everything else (corners, ragged last tiles, a halo that only grazes the border, images one tile wide or
+//             high, unaligned pointers or rows, images beyond the 32-bit lane offsets): bounds tests everywhere
+// `CA`: Layout's column halo (rup(2R, V)); `vec_ok`: 16-B aligned pointers and rows.
+enum TileClass : int { kTileInterior = 0, kTileCol = 1, kTileRow = 2, kTileGeneric = 3 };
+constexpr int kMaxInteriorN1 = 1 << 22;  // (64 rows x 2^22 columns x 8 B = 2^31: the 32-bit lane offsets of lane_ptr)
+__host__ __device__ inline int tile_class(int n0, int n1, int ty0, int tx0, int R, int CA, bool vec_ok) {
+  if (!vec_ok || (int64_t)n0 * n1 > 0x7fffffff || n1 > kMaxInteriorN1) return kTileGeneric;
+  const bool up = ty0 - 2 * R >= 0, down = ty0 + TY + 2 * R <= n0;
+  const bool left = tx0 - CA >= 0, right = tx0 + TX + CA <= n1;
+  if (up && down && left && right) return kTileInterior;
+  if (up && down && ((tx0 == 0 && right) || (tx0 + TX == n1 && left))) return kTileCol;
+  if (left && right && ((ty0 == 0 && down) || (ty0 + TY == n0 && up))) return kTileRow;
+  return kTileGeneric;
+}
+
+// ghost_cols_coop() for the one side a col tile has (side 0: the image's first columns, 1: its last): the same terms
+// with the same fma order into the same GH rows.  Every ghost column lies inside the PT rows here (the tile's own
+// columns end on the border, CA >= 2R).
+template <typename T, int R, int PTP>
+__device__ inline void ghost_cols_side(const T* __restrict__ k, const T* PT, T* GH, int side, int lt) {
+  using L = Layout<T, R>;
+  static_assert(L::CA >= 2 * R, "ghost columns and their taps inside the window");
+  for (int t = lt; t < R * TY; t += kThreads) {
+    const int m = t / TY, r = t % TY;
+    const int row = (side == 0 ? L::CA - R : L::CA + TX) + m;  // PT row of the ghost column
+    T g = T(0);
+#pragma unroll
+    for (int q = -R; q <= R; ++q) g = fma(k[q + R], PT[(row + q) * PTP + r], g);
+    GH[(side * R + m) * TY + r] = g;
+  }
+}
+
+// ghost_fix()'s correction step for NO outputs whose distance from the border is known at compile time, so that the
+// tap indices are constants (`k`: the taps in scalar registers) and the ghost terms sit at fixed offsets: term m is the
+// W-vector at gh + m * GP.  FAR = false: output o is position P0 + o of the axis (ghost positions -R + m, tap index
+// i - (-R + m) + R); FAR = true: output o is P0 - o positions before the last one (ghost positions n + m).  Per output
+// the same fma chain as ghost_fix(): m ascending, outputs beyond R of the border untouched.
+template <typename T, int R, int NO, int W, int GP, bool FAR, int P0>
+__device__ inline void ghost_sub(const T* __restrict__ k, const T* __restrict__ gh, T (&acc)[NO][W]) {
+#pragma unroll
+  for (int o = 0; o < NO; ++o) {
+    const int d = FAR ? P0 - o : P0 + o;  // distance from the border position
+    if (d < 0 || d >= R) continue;
+#pragma unroll
+    for (int m = 0; m < R; ++m) {
+      const int t = FAR ? -(d + 1) - m : d + R - m;
+      if (t < -R || t > R) continue;
+      const T kk = k[t + R];
+      T g[W];
+#pragma unroll
+      for (int v = 0; v < W; ++v) g[v] = gh[m * GP + v];
+#pragma unroll
+      for (int v = 0; v < W; ++v) acc[o][v] = fma(-kk, g[v], acc[o][v]);
+    }
+  }
+}
+
 // XCD-aware tile order (speed only): XCD group g = blockIdx % 8 owns a contiguous band of tiles.
 __device__ inline unsigned xcd_tile(unsigned bid, unsigned nb) {
   const unsigned q8 = nb >> 3, r8 = nb & 7u, g8 = bid & 7u;

@@ -1,5 +1,5 @@
 """Static instruction counts of the PGD tile kernel from a device-only assembly listing of csrc/pgd_tv2d.hip
-(hipcc <the Makefile's CXXFLAGS> --cuda-device-only -S pgd_tv2d.hip -o pgd.s):
+(hipcc <the Makefile's CXXFLAGS and PGD_FLAGS> --cuda-device-only -S pgd_tv2d.hip -o pgd.s):
 
     python3 scripts/pgd_window_isa.py pgd.s ["pgd_tv2d_kernelIfLi6E"]
 
