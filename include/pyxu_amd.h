@@ -639,9 +639,9 @@ int pxa_pgd_tv2d_last_kernel(void);
 int pxa_pgd_tile_trace(uint64_t* host_out, int n);
 /* Diagnostics (probe build only, else PXA_ERR_UNSUPPORTED): the launch timeline of the tile kernel's last launch under
  * PXA_TUNE_PGD_DIAG bit 5: per workgroup, in blockIdx order, 3 words -- s_memtime at its start, at its end, and
- * tile index | tile class << 32 (classes as pxa_pgd_tv2d_tile_classes) | XCC_ID << 36 | HW_ID[15:0] << 40 of the
- * workgroup's first wave; nwg <= 16384 workgroups.  The counter's base differs between XCDs and between CUs.  Bit 11 of the same key (probe build) runs col and row tiles on
- * the generic path. */
+ * tile index | tile class << 32 (0 interior, 1 col, 2 row, 3 generic, 4 corner) | XCC_ID << 36 | HW_ID[15:0] << 40 of
+ * the workgroup's first wave; nwg <= 16384 workgroups.  The counter's base differs between XCDs and between CUs.
+ * Bit 11 of the same key (probe build) runs col, row and corner tiles on the generic path, bit 12 corner tiles alone. */
 int pxa_pgd_tile_timeline(uint64_t* host_out, int nwg);
 int pxa_pgd_tv2d_step(int dtype, int64_t stack, int64_t y_images, int64_t n0, int64_t n1, int nt0, const int32_t* off0,
                       const double* coef0, int nt1, const int32_t* off1, const double* coef1, double h0, double h1,
@@ -869,6 +869,14 @@ int pxa_pds_step_la(int dtype, int algo, const int64_t* geom, const int32_t* nta
  * The fp64 kernel runs col and row tiles on its generic path: for fp64 read counts[1] + counts[2] + counts[3] as
  * generic.  Host only: no GPU is touched.  Returns PXA_OK or PXA_ERR_ARG. */
 int pxa_pgd_tv2d_tile_classes(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts);
+/* The same census with the corner class apart: counts[0 .. 4] = interior, col, row, corner, generic tiles.
+ *   corner:   the tile's own rows end exactly on the top or the bottom border with the 2R halo rows of the other side
+ *             inside, and its own columns end exactly on the left or the right border with the other side's halo
+ *             inside.  The fp32 kernel of reach R <= 6 runs these on the row class's code with the col class's column
+ *             part; for R = 7, 8 (kernels that spill registers already) and in fp64 they run as generic tiles: the census
+ *             is the geometry, for every R.
+ * counts[3] + counts[4] is pxa_pgd_tv2d_tile_classes' generic count; the other three agree.  Host only. */
+int pxa_pgd_tv2d_tile_census(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts);
 
 #ifdef __cplusplus
 }

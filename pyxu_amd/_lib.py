@@ -103,6 +103,7 @@ EXPORTS = {
     "pxa_pgd_tv2d_partials_count": (i32, [i64, i64, i64]),
     "pxa_pgd_tv2d_last_kernel": (i32, []),
     "pxa_pgd_tv2d_tile_classes": (i32, [i64, i64, i64, i32, i32, P_i64]),
+    "pxa_pgd_tv2d_tile_census": (i32, [i64, i64, i64, i32, i32, P_i64]),
     "pxa_pgd_tile_trace": (i32, [vp, i32]),
     "pxa_pgd_tile_timeline": (i32, [vp, i32]),
     "pxa_pgd_tv2d_plan": (i32, [i32, i64, i64, i64, i64, i32, P_i32, P_f64, i32, P_i32, P_f64, f64, f64, f64, f64, i32,

@@ -37,7 +37,9 @@
 // Tile classes (tile2d.hpp tile_class; fp32): a tile whose window lies inside the image is `interior` (no bounds tests);
 // one that ends exactly on one border of an aligned image is `col` or `row` and runs the interior code on its interior
 // axis, skipping the halo beyond the border and correcting the R boundary rows / columns of G from ghost terms with
-// compile-time tap indices; every other tile is `generic` (bounds tests, runtime-indexed corrections).
+// compile-time tap indices; one that ends on a row border and a column border at once is `corner` and runs the row
+// class's code with the col class's column part (R <= 6); every other tile is `generic` (bounds tests, runtime-indexed
+// corrections).
 #include "tile2d.hpp"
 #include <type_traits>
 
@@ -256,18 +258,37 @@ __device__ inline T* lane_ptr(T* img, int row0, int col0, int n1, int ru, unsign
   return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + (size_t)voff);
 }
 
-// The side of a col / row tile (tile2d.hpp tile_class): 0 when it holds the image's first columns / rows, 1 its last.
+// The side of a tile that ends on a border (tile2d.hpp tile_class): 0 when it holds the image's first rows / columns,
+// 1 its last.
+__device__ inline int row_side(int ty0) { return __builtin_amdgcn_readfirstlane(ty0 == 0 ? 0 : 1); }
+__device__ inline int col_side(int tx0) { return __builtin_amdgcn_readfirstlane(tx0 == 0 ? 0 : 1); }
+
+// Corner tiles end on a row border and a column border at once.  They run the row class's body, which takes the column
+// part (the skipped side vectors, ghost_cols_side, the col class's sweep corrections, the TV "first column") under the
+// wave-uniform flag `corner`: the four workgroups of a launch that are corners then execute code that the row tiles of
+// their XCD -- dispatched beside them, the top and bottom tile rows -- keep in the instruction cache, and only the
+// column part is theirs alone.  A fifth copy of the tile body, measured beside this form, gave the same corner life
+// (20.1 k against 20.3 k ticks median at 2048^2, R = 6; generic 30.3 k) from more code.
+// Whether a tile run by class C's body has a border column (`corner`: wave-uniform).
 template <int C>
-__device__ inline int tile_side(int ty0, int tx0) {
-  return __builtin_amdgcn_readfirstlane(C == kTileCol ? (tx0 == 0 ? 0 : 1) : (ty0 == 0 ? 0 : 1));
+__device__ inline bool has_col(bool corner) {
+  if constexpr (C == kTileCol) return true;
+  else if constexpr (C == kTileRow) return corner;
+  else return false;
 }
+// The reaches whose kernel has the corner part.  R = 7 and 8 keep their corners on the generic path, as fp64 does:
+// these two instantiations already spill (128 VGPRs at four workgroups per CU), and with the corner part they spill
+// more (R = 7: 204 -> 296 B of scratch per thread, R = 8: 620 -> 624 B), which every tile of the launch would pay for.
+template <int R>
+constexpr bool kCornerPart = R <= 6;
 
 // `C`: the tile's class.  Col and row tiles load as interior ones do, except that the halo vectors beyond their one
 // border -- the CV side vectors of every window row / the 2R rows of one vertical block, side vectors included --
-// are not loaded and stay zero; the own items (and so the window partials) are never among them.
+// are not loaded and stay zero; a corner tile skips both sets.  The own items (and so the window partials) are never
+// among them.
 template <typename T, int R, int C>
 __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const T* __restrict__ xs,
-                                 const T* __restrict__ xps, Window<T, R>& w, int lt) {
+                                 const T* __restrict__ xps, Window<T, R>& w, int lt, bool corner) {
   using L = Layout<T, R>;
   using W = Window<T, R>;
   constexpr int V = L::V;
@@ -276,7 +297,8 @@ __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const 
   const int n0 = p.n0, n1 = p.n1;
   int wv, ln;
   wave_lane(lt, wv, ln);
-  const int side = tile_side<C>(ty0, tx0);
+  const int rside = row_side(ty0), cside = col_side(tx0);
+  const bool colp = has_col<C>(corner);
 #pragma unroll
   for (int k = 0; k < W::K0; ++k) {
     int rl, gl, ru, gu;
@@ -284,8 +306,9 @@ __device__ inline void win_issue(const PgdParams<T>& p, int ty0, int tx0, const 
       if (!EDGE) {
         if ((C == kTileCol || C == kTileRow) && k >= W::KI) {
           const int r = rl + ru, g = gl + gu;
-          const bool outside = C == kTileCol ? (side == 0 ? g < W::CV : g >= W::CV + W::TV)
-                                             : (side == 0 ? r < 2 * R : r >= 2 * R + TY);
+          bool outside = false;
+          if constexpr (C == kTileRow) outside = rside == 0 ? r < 2 * R : r >= 2 * R + TY;
+          if (colp) outside = outside || (cside == 0 ? g < W::CV : g >= W::CV + W::TV);
           if (outside) {
 #pragma unroll
             for (int v = 0; v < V; ++v) w.xv[k][v] = w.pv[k][v] = T(0);
@@ -346,7 +369,9 @@ __host__ __device__ constexpr int pt_pitch() {
 
 // ---- pass A: PT[col][row] = (G0 yk)[row][col] for the TY tile rows and all A columns
 // Bytes of the ghost-term region of the PGD tile kernel: the boundary-column terms of a col or generic tile (tile2d.hpp
-// kGhBytes) or the boundary-row terms of a row tile (fp32: R rows of AC columns); a tile has one or the other.
+// kGhBytes) or the boundary-row terms of a row tile (fp32: R rows of AC columns).  A corner tile has both, one after the
+// other: its row terms are written and read inside pass A, wave by wave, and are dead at the barrier behind it; its
+// column terms are written behind that barrier.  So the region is the larger of the two, not their sum, for every R.
 template <typename T, int R>
 constexpr size_t kPgdGhBytes =
     sizeof(T) == 4 && (size_t)R * Layout<T, R>::AC * sizeof(T) > kGhBytes<T, R> ? (size_t)R * Layout<T, R>::AC * sizeof(T)
@@ -378,7 +403,7 @@ __device__ inline void ghost_rows_coop(const PgdParams<T>& p, const T* A, T* GH,
   }
 }
 
-// `C`: the tile's class.  Col tiles run the interior stream (their rows are interior); row tiles correct the items
+// `C`: the tile's class.  Col tiles run the interior stream (their rows are interior); row and corner tiles correct the items
 // within R rows of their border from the ghost rows of ghost_rows_coop, tap indices known at compile time per row group.
 template <typename T, int R, int C, int D = 0>
 __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T* KT, T* GH, int ty0, int tid = threadIdx.x) {
@@ -398,7 +423,7 @@ __device__ inline void pass_a(const PgdParams<T>& p, const T* A, T* PT, const T*
       if constexpr (C == kTileRow) {
         static_assert(KA == 1 && L::NPA % L::NA == 0 && 64 % L::NA == 0, "a column group is NA lanes of one wave");
         static_assert(V == 4 && L::NA == 8 && R <= 8, "the row groups within R of a border: two on each side");
-        const int side = tile_side<C>(ty0, 0);
+        const int side = row_side(ty0);
         ghost_rows_coop<T, R>(p, A, GH, side, a, b);
         sweep<T, R, V, L::AP, D>(A + (V * a) * L::AP + V * b, p.g0, acc);
         __builtin_amdgcn_wave_barrier();
@@ -445,15 +470,17 @@ constexpr int kTvxFloats = 9 * kTvxP0 + 9 * BlockB<T, R>::WR;
 
 // `C`: the tile's class.  Generic tiles test every q's pixel against the image; in a col or row tile the only pixels
 // outside are the column left of a first-column tile and the row above a top-row tile (q of the last column / row is
-// evaluated from the zeros beyond it, as everywhere), so only those halo evaluations are zeroed (`zq`).
+// evaluated from the zeros beyond it, as everywhere), so only those halo evaluations are zeroed (`zq`); a corner tile
+// can have both.
 template <typename T, int R, int C>
 __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, int wv, int ln, T (&yc)[2][4],
-                                T (&tv)[2][4]) {
+                                T (&tv)[2][4], bool corner) {
   using L = Layout<T, R>;
   using B = BlockB<T, R>;
   constexpr int CA = L::CA, AP = L::AP;
   constexpr bool EDGE = C == kTileGeneric;
-  const bool first = (C == kTileCol || C == kTileRow) && tile_side<C>(ty0, tx0) == 0;
+  const bool first_row = C == kTileRow && row_side(ty0) == 0;             // the row above the tile is outside
+  const bool first_col = has_col<C>(corner) && col_side(tx0) == 0;  // the column left of it is
   constexpr bool kExchange = (2 * R - 1) * AP >= 2 * kTvxFloats<T, R>;
   const int n0 = p.n0, n1 = p.n1;
   int rpl, cil, wr0, wc0;
@@ -504,12 +531,12 @@ __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, i
       if (ln < 32) {  // q0 of the row above the region
         const int tc = wc0 + ln;
         const T* h = A + (wr0 - 1 + 2 * R) * AP + CA + tc;
-        qat(h[0], h[AP], h[1], ty0 + wr0 - 1, tx0 + tc, hq0, hq1, C == kTileRow && first && wr0 == 0);
+        qat(h[0], h[AP], h[1], ty0 + wr0 - 1, tx0 + tc, hq0, hq1, first_row && wr0 == 0);
         E0[ln] = hq0;
       } else {  // q1 of the column left of the region
         const int j = ln - 32, tc = wc0 - 1;
         const T* h = A + (wr0 + j + 2 * R) * AP + CA + tc;
-        qat(h[0], h[AP], h[1], ty0 + wr0 + j, tx0 + tc, hq0, hq1, C == kTileCol && first && wc0 == 0);
+        qat(h[0], h[AP], h[1], ty0 + wr0 + j, tx0 + tc, hq0, hq1, first_col && wc0 == 0);
         E1[j] = hq1;
       }
     }
@@ -547,7 +574,7 @@ __device__ inline void tv_block(const PgdParams<T>& p, T* A, int ty0, int tx0, i
 #pragma unroll
       for (int c = 0; c < 5; ++c)
         qat(yr[c], yn[c], yr[c + 1], ty0 + r0 - 1 + r, tx0 + c0 - 1 + c, q0[c], q1[c],
-            first && (C == kTileCol ? c == 0 && c0 == 0 : r == 0 && r0 == 0));
+            (first_col && c == 0 && c0 == 0) || (first_row && r == 0 && r0 == 0));
     };
     T yr[6], yn[6];
     yrow(0, yr);
@@ -806,7 +833,7 @@ constexpr int kRingB = 4;
 template <typename T, int R, int C, typename Mark>
 __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, const T* KT, const T* GH, int ty0, int tx0,
                                      const T* __restrict__ bs, const T* __restrict__ xrs, T* __restrict__ xns,
-                                     bool want_part, double& part_d, double& part_x, int tid, Mark&& tmark) {
+                                     bool want_part, double& part_d, double& part_x, int tid, Mark&& tmark, bool corner) {
   using L = Layout<T, R>;
   using B = BlockB<T, R>;
   constexpr int CA = L::CA, PTP = B::PTP;
@@ -856,7 +883,7 @@ __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, c
   } else {
     const T* src = PT + (CA - 2 * R + c0) * PTP + r0;
     if constexpr (kRowsLiveB<R>) {
-      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv, corner);
       tmark(5);
       load_epilogue();
       sweep_w<T, R, 4, 2, PTP>(src, p.g1, acc);
@@ -868,18 +895,18 @@ __device__ inline void pass_b_blocks(const PgdParams<T>& p, T* A, const T* PT, c
         asm volatile("" : "+s"(g1[k]));
       }
       RowSweep<T, R, 4, 2, PTP, kRingB> sw;
-      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv);
+      tv_block<T, R, C>(p, A, ty0, tx0, wv, ln, yc, tv, corner);
       tmark(5);
       load_epilogue();
       sw.start(src);
       sw.run(src, g1, acc);
     }
     if (edge_cols) ghost_fix_pre_w<T, R, 4, 2, TY>(tx0 + c0, n1, r0, GH, KT + kKT, acc);
-    if constexpr (C == kTileCol) {
+    if (has_col<C>(corner)) {
       // ghost_fix_pre_w specialised on the side and on the block's column: only the blocks that hold a column within
       // R of the border do anything, with constant tap indices (p.k1) and GH offsets
       static_assert(R <= 8, "columns within R of a border: two blocks on each side");
-      if (tile_side<C>(ty0, tx0) == 0) {
+      if (col_side(tx0) == 0) {
         if (c0 == 0) ghost_sub<T, R, 4, 2, TY, false, 0>(p.k1, GH + r0, acc);
         if (R > 4 && c0 == 4) ghost_sub<T, R, 4, 2, TY, false, 4>(p.k1, GH + r0, acc);
       } else {
@@ -1009,7 +1036,7 @@ __device__ inline void pass_b_staged(const PgdParams<T>& p, T* A, T* PT, const T
 template <typename T, int R, int C, int D>
 __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
                                      const T* __restrict__ bs, T* __restrict__ xns, double* __restrict__ partials,
-                                     const T* __restrict__ xrs, const int tid) {
+                                     const T* __restrict__ xrs, const int tid, bool corner) {
   using L = Layout<T, R>;
   T* A = reinterpret_cast<T*>(smem);
   T* PT = A + L::AR * L::AP;
@@ -1034,13 +1061,13 @@ __device__ inline void pgd_tile_body(const PgdParams<T>& p, unsigned char* smem,
     ghost_cols_coop<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, tx0, n1, tid);
     __syncthreads();
   }
-  if constexpr (C == kTileCol) {  // the one side that exists
-    ghost_cols_side<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, tile_side<C>(ty0, tx0), tid);
+  if (has_col<C>(corner)) {  // the one side that exists (a corner's row terms are dead behind the barrier above)
+    ghost_cols_side<T, R, pt_pitch<T, R>()>(p.k1, PT, GH, col_side(tx0), tid);
     __syncthreads();
   }
   tmark(4);
   if constexpr (sizeof(T) == 4) {  // no barrier from here on: each thread finishes its own block
-    pass_b_blocks<T, R, C>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
+    pass_b_blocks<T, R, C>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark, corner);
   } else {
     pass_b_staged<T, R, EDGE, D>(p, A, PT, KT, GH, ty0, tx0, bs, xrs, xns, want_part, part_d, part_x, tid, tmark);
   }
@@ -1088,7 +1115,8 @@ __device__ inline void win_partials(const Window<T, R>& w, double* __restrict__ 
 template <typename T, int R, int C>
 __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsigned tile, int ty0, int tx0,
                                 const T* __restrict__ xs, const T* __restrict__ xps, const T* __restrict__ bs,
-                                T* __restrict__ xns, double* __restrict__ partials, const T* __restrict__ xrs) {
+                                T* __restrict__ xns, double* __restrict__ partials, const T* __restrict__ xrs,
+                                bool corner = false) {
   using L = Layout<T, R>;
   T* A = reinterpret_cast<T*>(smem);
   T* KT = A + L::AR * L::AP + L::AC * L::PTP;
@@ -1111,7 +1139,7 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
     for (int i = tid; i < L::AR * L::AP; i += kThreads) A[i] = T(0);
   } else {
     Window<T, R> w;
-    win_issue<T, R, C>(p, ty0, tx0, xs, xps, w, tid);
+    win_issue<T, R, C>(p, ty0, tx0, xs, xps, w, tid, corner);
     win_store<T, R>(p, A, w, tid);
     if (p.win_part && partials != nullptr) win_partials<T, R>(w, partials, tile, tid);
   }
@@ -1127,7 +1155,7 @@ __device__ inline void pgd_tile(const PgdParams<T>& p, unsigned char* smem, unsi
   int btid = tid;
   if constexpr (sizeof(T) == 8) asm volatile("" : "+v"(btid));
   pgd_tile_body<T, R, C, PXA_PGD_SWEEP_DEPTH>(p, smem, tile, ty0, tx0, bs, xns, p.win_part ? nullptr : partials, xrs,
-                                                 btid);
+                                                 btid, corner);
 }
 
 // (Opt-in: PXA_RELERR_SINK=1; gfx950-specific.)  The hand-off below uses no release / acquire: it is the first row
@@ -1235,15 +1263,18 @@ __global__ void __launch_bounds__(kThreads, 4) pgd_tv2d_kernel(PgdParams<T> p, c
   [[maybe_unused]] int tl_cls = kTileGeneric;
   if constexpr (sizeof(T) == 4) {
     int cls = __builtin_amdgcn_readfirstlane(tile_class(p.n0, p.n1, ty0, tx0, R, L::CA, p.vec_ok));
-    // measurement probe only: col and row tiles on the generic path, as before the classes existed
+    // measurement probe only: col, row and corner tiles on the generic path, as before the classes existed
     if (kProbes && (p.diag & 2048) && cls != kTileInterior) cls = kTileGeneric;
+    // (A/B builds: corners alone on the generic path, the dispatch before the corner class)
+    if (kProbes && (p.diag & 4096) && cls == kTileCorner) cls = kTileGeneric;
     if (kProbes) tl_cls = cls;
     if (cls == kTileInterior)
       pgd_tile<T, R, kTileInterior>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
     else if (cls == kTileCol)
       pgd_tile<T, R, kTileCol>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
-    else if (cls == kTileRow)
-      pgd_tile<T, R, kTileRow>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
+    else if (cls == kTileRow || (kCornerPart<R> && cls == kTileCorner))  // one call: one copy of the row class's body
+      pgd_tile<T, R, kTileRow>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs,
+                               kCornerPart<R> && cls == kTileCorner);
     else
       pgd_tile<T, R, kTileGeneric>(p, smem_raw, tile, ty0, tx0, xs, xps, bs, xns, partials, xrs);
   } else {
@@ -1435,15 +1466,39 @@ int pxa_pgd_tv2d_partials_count(int64_t stack, int64_t n0, int64_t n1) {
   return (int)t;
 }
 
-int pxa_pgd_tv2d_tile_classes(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts) {
-  PXA_CHECK_ARG(counts != nullptr && stack >= 1 && n0 >= 1 && n1 >= 1 && n0 <= 0x7fffffff && n1 <= 0x7fffffff);
+// the fp32 kernel's dispatch over every tile of the stack: by[c] = tiles of TileClass c
+static int pgd_tile_census(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t (&by)[5]) {
+  PXA_CHECK_ARG(stack >= 1 && n0 >= 1 && n1 >= 1 && n0 <= 0x7fffffff && n1 <= 0x7fffffff);
   PXA_CHECK_ARG(R >= 1 && R <= kMaxR);
-  // the fp32 kernel's dispatch: 4-element vectors, the column halo of Layout<float, R>
+  // 4-element vectors, the column halo of Layout<float, R>
   constexpr int V = kVecN<float>;
   const bool vec_ok = aligned != 0 && n1 % V == 0;
-  for (int c = 0; c < 4; ++c) counts[c] = 0;
+  for (int64_t& c : by) c = 0;
   for (int64_t ty0 = 0; ty0 < n0; ty0 += TY)
-    for (int64_t tx0 = 0; tx0 < n1; tx0 += TX) counts[tile_class((int)n0, (int)n1, (int)ty0, (int)tx0, R, rup(2 * R, V), vec_ok)] += stack;
+    for (int64_t tx0 = 0; tx0 < n1; tx0 += TX) by[tile_class((int)n0, (int)n1, (int)ty0, (int)tx0, R, rup(2 * R, V), vec_ok)] += stack;
+  return PXA_OK;
+}
+
+int pxa_pgd_tv2d_tile_classes(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts) {
+  PXA_CHECK_ARG(counts != nullptr);
+  int64_t by[5];
+  if (const int e = pgd_tile_census(stack, n0, n1, R, aligned, by)) return e;
+  counts[0] = by[kTileInterior];
+  counts[1] = by[kTileCol];
+  counts[2] = by[kTileRow];
+  counts[3] = by[kTileGeneric] + by[kTileCorner];  // four counts: corners under generic
+  return PXA_OK;
+}
+
+int pxa_pgd_tv2d_tile_census(int64_t stack, int64_t n0, int64_t n1, int R, int aligned, int64_t* counts) {
+  PXA_CHECK_ARG(counts != nullptr);
+  int64_t by[5];
+  if (const int e = pgd_tile_census(stack, n0, n1, R, aligned, by)) return e;
+  counts[0] = by[kTileInterior];
+  counts[1] = by[kTileCol];
+  counts[2] = by[kTileRow];
+  counts[3] = by[kTileCorner];
+  counts[4] = by[kTileGeneric];
   return PXA_OK;
 }
 

@@ -474,18 +474,24 @@ __device__ inline void ghost_fix_pre_w(int i0, int n, int cc, const T* __restric
 //   col       the window's rows lie inside, the tile's own columns end exactly on one border (tx0 == 0 or tx0 + TX == n1)
 //             and the other side's CA halo is inside
 //   row       the mirror image: columns interior, ty0 == 0 or ty0 + TY == n0, the other side's 2R rows inside
-//   generic   everything else (corners, ragged last tiles, a halo that only grazes the border, images one tile wide or
+//   corner    both at once: own rows end exactly on one horizontal border with the other side's 2R rows inside, own
+//             columns end exactly on one vertical border with the other side's CA halo inside (all four orientations)
+//   generic   everything else (ragged last tiles, a halo that only grazes the border, images one tile wide or
 //             high, unaligned pointers or rows, images beyond the 32-bit lane offsets): bounds tests everywhere
 // `CA`: Layout's column halo (rup(2R, V)); `vec_ok`: 16-B aligned pointers and rows.
-enum TileClass : int { kTileInterior = 0, kTileCol = 1, kTileRow = 2, kTileGeneric = 3 };
+// (kTileGeneric keeps its value: pxa_pgd_tv2d_tile_classes indexes its four counts by it.)
+enum TileClass : int { kTileInterior = 0, kTileCol = 1, kTileRow = 2, kTileGeneric = 3, kTileCorner = 4 };
 constexpr int kMaxInteriorN1 = 1 << 22;  // (64 rows x 2^22 columns x 8 B = 2^31: the 32-bit lane offsets of lane_ptr)
 __host__ __device__ inline int tile_class(int n0, int n1, int ty0, int tx0, int R, int CA, bool vec_ok) {
   if (!vec_ok || (int64_t)n0 * n1 > 0x7fffffff || n1 > kMaxInteriorN1) return kTileGeneric;
   const bool up = ty0 - 2 * R >= 0, down = ty0 + TY + 2 * R <= n0;
   const bool left = tx0 - CA >= 0, right = tx0 + TX + CA <= n1;
+  const bool row_end = (ty0 == 0 && down) || (ty0 + TY == n0 && up);
+  const bool col_end = (tx0 == 0 && right) || (tx0 + TX == n1 && left);
   if (up && down && left && right) return kTileInterior;
-  if (up && down && ((tx0 == 0 && right) || (tx0 + TX == n1 && left))) return kTileCol;
-  if (left && right && ((ty0 == 0 && down) || (ty0 + TY == n0 && up))) return kTileRow;
+  if (up && down && col_end) return kTileCol;
+  if (left && right && row_end) return kTileRow;
+  if (row_end && col_end) return kTileCorner;
   return kTileGeneric;
 }
 

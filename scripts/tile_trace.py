@@ -1,12 +1,13 @@
 """Development probe (probe build: make -C pyxu_amd/csrc probe, PXA_LIB_PATH=build/libpyxu_amd_probe.so): the tile
 kernel (pgd_tv2d_kernel) from its s_memtime trace (PXA_TUNE_PGD_DIAG bit 5).
 
-  python scripts/tile_trace.py [n] [sigma] [--timeline] [--generic] [--save=raw.npy]
+  python scripts/tile_trace.py [n] [sigma] [--timeline] [--generic] [--corners-generic] [--save=raw.npy]
 
 Phase durations of workgroups 0 (corner tile), 9 and grid/2 + 8 (interior tiles at 2048^2), grid-1 (first-column tile)
 and 8 (top-row tile).  --timeline: also the launch timeline from every workgroup's start / end stamps, per XCD (the
-counter's base differs between XCDs and between CUs, so stamps are taken relative to the first start on the same CU).  --generic: col and row
-tiles on the generic path (bit 11), the dispatch before the tile classes existed."""
+counter's base differs between XCDs and between CUs, so stamps are taken relative to the first start on the same CU).  --generic: col, row
+and corner tiles on the generic path (bit 11), the dispatch before the tile classes existed; --corners-generic: corner
+tiles alone (bit 12), the dispatch before the corner class."""
 import ctypes as ct
 import sys
 
@@ -22,7 +23,7 @@ flags = [a for a in sys.argv[1:] if a.startswith("--")]
 pos = [a for a in sys.argv[1:] if not a.startswith("--")]
 n = int(pos[0]) if len(pos) > 0 else 2048
 sigma = float(pos[1]) if len(pos) > 1 else 2.0
-diag = 32 | (2048 if "--generic" in flags else 0)
+diag = 32 | (2048 if "--generic" in flags else 0) | (4096 if "--corners-generic" in flags else 0)
 g = torch.Generator(device="cuda").manual_seed(0)
 x, xp, b = (torch.rand((n, n), device="cuda", generator=g) for _ in range(3))
 out = torch.empty_like(x)
@@ -42,7 +43,8 @@ if "--timeline" in flags:
         np.save(save[0], tl)
 for k, v in prev:
     _dev.tuning(k, v)
-print(f"n = {n}, sigma = {sigma}, dispatch: {'generic edge tiles' if diag & 2048 else 'tile classes'}")
+print(f"n = {n}, sigma = {sigma}, dispatch: "
+      f"{'generic edge tiles' if diag & 2048 else 'tile classes, corners generic' if diag & 4096 else 'tile classes'}")
 # fp32 (row-major pass-B blocks, no staging): H^T y loads + first PT rows issued + TV chain, the G1 sweep, finish in
 # registers + x_new stores; fp64 would be pass B, H^T y loads + O staging, row-major epilogue (this probe runs fp32)
 names = ["load", "B1", "passA", "B2(+ghost)", "loads+TV", "sweep", "epilogue"]
@@ -55,7 +57,7 @@ for slot, lab in enumerate(["wg0", "wg9", "wg n/2+8", "wg n-1", "wg8"]):
               f"| total {tr[slot, w, 7] - tr[slot, w, 0]:6d}")
 
 if "--timeline" in flags:
-    CLS = ["interior", "col", "row", "generic"]
+    CLS = ["interior", "col", "row", "generic", "corner"]  # (the kernel's TileClass values)
     tl = tl.astype(np.int64).reshape(nwg, 3)
     tile, cls = tl[:, 2] & 0xFFFFFFFF, (tl[:, 2] >> 32) & 15
     xcc, hw = (tl[:, 2] >> 36) & 15, (tl[:, 2] >> 40) & 0xFFFF
@@ -68,7 +70,7 @@ if "--timeline" in flags:
     life = tl[:, 1] - tl[:, 0]
     print("life per class (median / max over the launch): " + "  ".join(
         f"{CLS[c]} {int(np.median(life[cls == c]))} / {int(life[cls == c].max())} (n={int((cls == c).sum())})"
-        for c in range(4) if (cls == c).any()))
+        for c in range(len(CLS)) if (cls == c).any()))
     tails = []
     for x_ in sorted(set(xcc.tolist())):
         idx = np.nonzero(xcc == x_)[0]
@@ -87,6 +89,13 @@ if "--timeline" in flags:
         last = np.argsort(en)[::-1][:4]
         print("        ends last: " + ", ".join(
             f"tile ({tix[i] // tiles1},{tix[i] % tiles1}) {CLS[c[i]]} round {rnd[i]} start {st[i]} end {en[i]}" for i in last))
+        late = np.argsort(st)[::-1][:4]  # the XCD's last dispatches: the slots that freed last
+        print("        starts last: " + ", ".join(
+            f"tile ({tix[i] // tiles1},{tix[i] % tiles1}) {CLS[c[i]]} start {st[i]}" for i in late))
+        slow = np.nonzero(c >= 3)[0]  # generic and corner tiles of this XCD
+        if len(slow):
+            print("        generic / corner: " + ", ".join(
+                f"tile ({tix[i] // tiles1},{tix[i] % tiles1}) {CLS[c[i]]} round {rnd[i]} start {st[i]} end {en[i]}" for i in slow[:8]))
         # a compute unit is done when the last of its workgroups ends: the idle time of its slots until the XCD's last end
         ce = np.array([en[cu[idx] == u].max() for u in sorted(set(cu[idx].tolist()))])
         tails.append((en.max() - np.median(ce), float(np.mean(en.max() - ce))))
