@@ -347,6 +347,41 @@ int pxa_proxadam_sub_step(int dtype, int kind, int k, int64_t rows, int64_t n, d
                           double pw, const void* xt, const void* psi, const void* z_prev, const void* z, void* z_new,
                           void* out, void* work, uint32_t* nrun_host, uint32_t* flag, uint32_t seq, void* stream);
 
+/* Langevin samplers (experimental/sampler/_sampler.py:105-488, statistics.py:126-171).  All arithmetic is in the
+ * working type T, every operation rounded to T and none contracted into an FMA.  A call moves groups of 16 bytes with
+ * 16-byte accesses where every operand is 16-byte aligned at the boundaries of the global groups (for e0 a multiple of
+ * the group size: where every pointer is 16-byte aligned) and element by element otherwise; both give the same bits.
+ *
+ * pxa_philox_normal: out[i] = the standard normal of global element e0 + i, i < n, a function of (seed, step, e0 + i)
+ * alone.  Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; Weyl constants 0x9E3779B9, 0xBB67AE85), key = (seed lo,
+ * seed hi), counter = (g lo, g hi, step lo, step hi) with g the element's group, giving words w0 .. w3:
+ *   f32, group of 4: elements 4g, 4g + 1 from (w0, w1), elements 4g + 2, 4g + 3 from (w2, w3):
+ *                    u1 = ((w >> 8) + 1) 2^-24, u2 = (w' >> 8) 2^-24
+ *   f64, group of 2: u1 = (((w0 2^32 + w1) >> 11) + 1) 2^-53, u2 = ((w2 2^32 + w3) >> 11) 2^-53
+ *   r = sqrt(-2 ln u1); the pair is r cospi(2 u2), r sinpi(2 u2)  (accurate log and sincospi)
+ * A range that starts or ends inside a group writes its own elements only.
+ *
+ * pxa_langevin_step: one chain step over n flat elements (stacked chains: one longer array):
+ *   x' = (x - gamma (grad + m)) + c z,   gamma cast to T,  c = (T)sqrt(2 gamma) formed in double from the T gamma
+ * z = noise[i], or with noise == NULL the normal pxa_philox_normal writes for (seed, step, e0 + i), the same bits.
+ * m is the Moreau-Yosida gradient (x - prox_{lam g}(x)) / lam of an element-wise g, t = (T)(lam pw), division by lam:
+ *   kind 0  no g: m absent              1  pw ||.||_1: clip(x, -t, t) / lam        2  x >= 0: min(x, 0) / lam
+ *   3  pw ||.||_1 + (x >= 0): min(x, t) / lam        4  |x| <= pw: (x - clip(x, -pw, pw)) / lam
+ * A NaN in x, grad or noise stays in its element.  x_out may be x and aliases nothing else.  3 array streams with device
+ * noise, 4 with supplied noise.
+ *
+ * pxa_online_moments: sample number k (0-based) folded into the Welford state of the centred moments up to `order`
+ * (2 .. 4): mean (n of T) and sums (order - 1 planes of n doubles, plane r - 2 the corrected sum of order r).  k == 0:
+ * mean = x, sums = 0.  Otherwise, in the order of statistics.py:159-168 (orders descending, so every order reads the
+ * lower orders' previous sums): temp = (x - mean) / (T)(k + 1), a = -temp and b = (T)k temp in T; their powers, the
+ * binomial terms C(r, s) S_s a^(r - s), k a^r, b^r and the sums in double; then mean = mean (T)(k / (k + 1)) +
+ * x / (T)(k + 1) in T.  One launch; x is none of the outputs. */
+int pxa_philox_normal(int dtype, int64_t n, uint64_t seed, uint64_t step, uint64_t e0, void* out, void* stream);
+int pxa_langevin_step(int dtype, int kind, int64_t n, double gamma, double lam, double pw, uint64_t seed, uint64_t step,
+                      uint64_t e0, const void* x, const void* grad, const void* noise, void* x_out, void* stream);
+int pxa_online_moments(int dtype, int order, int64_t k, int64_t n, const void* x, void* mean, double* sums,
+                       void* stream);
+
 /* RelError statistics from the fused PGD step's per-tile partials (pxa_pgd_tv2d_step[_y] with
  * `partials`): out[0 * rows + r] = sum (x_new - x)^2 and out[1 * rows + r] = sum x^2 over the per_row
  * consecutive tiles of stack row r, fixed summation order.  At stop_rate 1 the criterion's stored x_prev

@@ -837,6 +837,76 @@ def proxadam_running(fb, seq):
     return int(fb.values.view(np.uint32)[0])
 
 
+# ------------------------------------------------------------------ Langevin samplers (csrc/sampler.hip)
+_U64 = (1 << 64) - 1
+
+
+def _flat_operand(t, name, n, like):
+    """A contiguous device operand of n elements of like's dtype, taken as it is (a view may start off a 16-byte
+    boundary: the kernels then go element by element)."""
+    if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dtype == like.dtype and t.numel() == n):
+        raise ValueError(f"sampler: {name} must be a contiguous device tensor of {n} elements of dtype {like.dtype}")
+    return t
+
+
+def _counter(v, name):
+    v = int(v)
+    if not 0 <= v <= _U64:
+        raise ValueError(f"sampler: {name} must fit 64 unsigned bits, got {v}")
+    return v
+
+
+def philox_normal(out, seed, step, e0=0):
+    """pxa_philox_normal: out (flat) = the standard normals of global elements e0 .. e0 + out.numel() - 1 of the
+    stream (seed, step) (include/pyxu_amd.h)."""
+    dtcode(out)
+    _flat_operand(out, "out", out.numel(), out)
+    check(lib.pxa_philox_normal(dtcode(out), out.numel(), _counter(seed, "seed"), _counter(step, "step"),
+                                _counter(e0, "e0"), ptr(out), stream()), "pxa_philox_normal")
+    return out
+
+
+def langevin_step(kind, gamma, lam, pw, x, grad, x_out, noise=None, seed=0, step=0, e0=0):
+    """pxa_langevin_step: x_out = (x - gamma (grad + m)) + sqrt(2 gamma) z, m the Moreau-Yosida gradient of the
+    element-wise g of `kind` (0: none, else PROX_*), z = noise or the Philox normal of (seed, step, e0 + i).  x_out
+    may be x."""
+    if kind not in (0, PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX):
+        raise ValueError(f"langevin_step: unknown kind {kind}")
+    dtcode(x)
+    n = x.numel()
+    ops = dict(x=x, grad=grad, x_out=x_out)
+    if noise is not None:
+        ops["noise"] = noise
+    for name, t in ops.items():
+        _flat_operand(t, name, n, x)
+    if x_out.data_ptr() in [t.data_ptr() for k, t in ops.items() if k not in ("x", "x_out")]:
+        raise ValueError("langevin_step: x_out may alias x only")
+    if not float(gamma) > 0 or (kind != 0 and not float(lam) > 0):
+        raise ValueError(f"langevin_step: gamma and lam must be positive, got {(gamma, lam)}")
+    check(lib.pxa_langevin_step(dtcode(x), int(kind), n, float(gamma), float(lam), float(pw), _counter(seed, "seed"),
+                                _counter(step, "step"), _counter(e0, "e0"), ptr(x), ptr(grad),
+                                ptr(noise) if noise is not None else None, ptr(x_out), stream()), "pxa_langevin_step")
+    return x_out
+
+
+def online_moments(order, k, x, mean, sums):
+    """pxa_online_moments: sample number k (0-based) folded into mean (x's dtype) and sums ((order - 1, n) float64)."""
+    if order not in (2, 3, 4) or int(k) < 0:
+        raise ValueError(f"online_moments: order must be 2, 3 or 4 and k >= 0, got {(order, k)}")
+    dtcode(x)
+    n = x.numel()
+    _flat_operand(x, "x", n, x)
+    _flat_operand(mean, "mean", n, x)
+    if not (hasattr(sums, "is_cuda") and sums.is_cuda and sums.is_contiguous() and sums.dtype == _torch().float64
+            and sums.numel() == (order - 1) * n):
+        raise ValueError(f"online_moments: sums must be a contiguous float64 device tensor of {order - 1} x {n}")
+    if mean.data_ptr() == x.data_ptr():
+        raise ValueError("online_moments: mean must not alias x")
+    check(lib.pxa_online_moments(dtcode(x), int(order), int(k), n, ptr(x), ptr(mean), ptr(sums), stream()),
+          "pxa_online_moments")
+    return mean, sums
+
+
 def dense_normal_pfold(A, r, p, p_new, rr, rr_out, fb, seq, s, d, work, pdot):
     """pxa_dense_normal_pdot_pfold: p_new = r + beta p (the CG's previous p update, beta from cg_update_xr's ||r'||^2
     partials at pdot + 64 doubles and `rr`), then Y = s A^T (A p_new) + d p_new and the <p_new, Y> partials into

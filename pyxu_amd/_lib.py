@@ -71,6 +71,10 @@ EXPORTS = {
     "pxa_proxadam_sub_init": (i32, [i64, i64, vp, vp]),
     "pxa_proxadam_sub_step": (i32, [i32, i32, i32, i64, i64, f64, f64, f64, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                     ct.c_uint32, vp]),
+    "pxa_philox_normal": (i32, [i32, i64, ct.c_uint64, ct.c_uint64, ct.c_uint64, vp, vp]),
+    "pxa_langevin_step": (i32, [i32, i32, i64, f64, f64, f64, ct.c_uint64, ct.c_uint64, ct.c_uint64, vp, vp, vp, vp,
+                                vp]),
+    "pxa_online_moments": (i32, [i32, i32, i64, i64, vp, vp, vp, vp]),
     "pxa_stencil_axis": (i32, [i32, i64, i32, P_i64, i32, i32, P_i32, P_f64, i32, vp, i64, vp, i64, f64, vp]),
     "pxa_stencil_sep_workspace_bytes": (sz, [i32, i64, i32, P_i64, P_int]),
     "pxa_stencil_sep": (i32, [i32, i64, i32, P_i64, P_int, P_i32, P_f64, vp, i64, vp, i64, f64, vp, vp]),
