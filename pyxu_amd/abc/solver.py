@@ -5,6 +5,7 @@ Same execution modes (BLOCK / ASYNC / MANUAL), stop/log/writeback rates, history
 thread, exception capture and ``data.npz`` checkpoint format.  The math state lives on the MI355X;
 device -> host copies happen only at stop-criterion evaluations and at writeback.
 """
+import collections
 import datetime as dt
 import enum
 import logging
@@ -19,6 +20,7 @@ import threading
 import numpy as np
 
 import pyxu_amd.runtime as pxrt
+from pyxu_amd.abc._stoplink import SolverState
 from pyxu_amd.util import to_NUMPY
 
 __all__ = ["Mode", "Solver", "StoppingCriterion"]
@@ -111,7 +113,7 @@ class Solver:
 
     def __init__(self, *, folder=None, exist_ok=False, stop_rate=1, writeback_rate=None, verbosity=None,
                  show_progress=True, log_var=frozenset(), _internal=False):
-        self._mstate = dict()
+        self._mstate = SolverState()  # math state only; what the step and the stop criteria tell each other: .link
         self._astate = dict(history=None, idx=0, log_rate=None, log_var=None, logger=None, stdout=None, stop_crit=None,
                             stop_rate=None, track_objective=None, wb_rate=None, workdir=None, mode=None, active=None,
                             worker=None, internal=bool(_internal), lock=threading.RLock())
@@ -429,14 +431,7 @@ class Solver:
         # batch: at stop_rate 1 the host, not the device, bounds the step, and one record per check cost
         # ~5 us of it; r05d host profile)
         if len(ast["pending"]) >= self._SPEC_BATCH:
-            with ast["lock"]:
-                if len(ast["pending"]) >= self._SPEC_BATCH:
-                    items = ast["pending"][: self._SPEC_BATCH]
-                    del ast["pending"][: self._SPEC_BATCH]
-                    # unflushed at most _RECORD_LAG lines: a reader of solver.log lags by at most one batch
-                    n = ast.get("unflushed", 0) + len(items)
-                    ast["unflushed"] = 0 if n >= self._RECORD_LAG else n
-                    self._record_batch(items, flush=n >= self._RECORD_LAG)
+            self._write_deferred(self._SPEC_BATCH)
         if resolve():
             ast["idx"] -= 1
             self._spec_rollback(token)
@@ -555,8 +550,12 @@ class Solver:
     # is enqueued (its statistics folded by the device into a ring of host flag buffers) and the next step launched
     # at once; checks are resolved in order as their statistics land.  The state at every unresolved check is held
     # (references: the solver never writes a tensor it still references), so when check j says stop, the steps
-    # launched after it are dropped and the solver ends in the state of check j.  Decisions, iterates, history
-    # records, log lines, MaxIter counts and steps() items are the synchronous path's (tests/test_gpu_solver_lag.py).
+    # launched after it are dropped and the solver ends in the state of check j, its criteria too.  With the epilogue
+    # statistics (_LAG_WINDOW off) everything is the synchronous path's bit for bit: decisions, iterates, history
+    # records, log lines, MaxIter counts, steps() items.  With the window statistics (the default) the RelError values
+    # are the same sums added in another order: they agree with the synchronous path's to rounding, so where a value
+    # sits at eps within rounding the decision, and with it the stop iteration, can differ; everything else follows
+    # from the decisions exactly as on the synchronous path (tests/test_gpu_solver_lag.py).
     # Applies to stop_rate 1 in BLOCK / MANUAL mode with an OR of MaxIter and one fused-path RelError, no
     # checkpoints, no objective tracking, and a solver that can restore a check's state (_lag_supported).
     _LAG = int(os.environ.get("PXA_STOP_LAG", "8"))
@@ -619,19 +618,19 @@ class Solver:
         return r, maxs
 
     class _LagCheck:
-        __slots__ = ("idx", "resolve", "pre", "snap", "stamp", "log", "ready", "counts", "rel_prev", "post", "info")
+        # snap, rel: the solver's and the RelError leaf's state the check sees (_lag_snapshot, RelError.snapshot);
+        # counts: the MaxIter leaves' counts once it ran
+        __slots__ = ("idx", "resolve", "pre", "snap", "stamp", "log", "ready", "counts", "rel", "post", "info")
 
     def _lag_loop(self, plan):
         """Generator running the fit to its end: yields the synchronous path's steps() item once per check that did
         not stop (so BLOCK mode just drains it), up to _LAG checks behind the launches."""
-        import collections
-
         rel, maxs = plan
         ast, mst = self._astate, self._mstate
         crit = ast["stop_crit"]
         depth = self._LAG
-        rel._nbufs = depth + 3  # flag buffers: the checks in flight, the one being resolved, the next launch's
-        rel._in_kernel_fold = self._LAG_INKERNEL
+        # flag buffers: the checks in flight, the one being resolved, the next launch's
+        rel.lag_configure(depth + 3, self._LAG_INKERNEL)
         log_on = not ast.get("internal")
         prec = pxrt.getPrecision().value
         pend = collections.deque()
@@ -641,16 +640,16 @@ class Solver:
             while True:
                 idx = ast["idx"]
                 e = Solver._LagCheck()
-                e.idx, e.snap, e.rel_prev = idx, self._lag_snapshot(), rel._x_prev
+                e.idx, e.snap, e.rel = idx, self._lag_snapshot(), rel.snapshot()
                 # window statistics need a next launch: not for the check at which MaxIter ends the run
                 last = False  # MaxIter ends the run at this check
                 for m in maxs:
-                    last = last or m._i + 1 > m._n
-                rel._window_stats = win and not last
+                    last = last or m.fires_next()
+                rel.want_window(win and not last)
                 e.resolve = crit.stop_async(mst)
                 e.pre = crit.info()  # MaxIter counts of this check (the RelError value is filled in when resolved)
-                e.counts = [m._i for m in maxs]
-                kind, probe = getattr(rel, "_last_async", ("sync", None))
+                e.counts = [m.count for m in maxs]
+                kind, probe = rel.last_async
                 e.ready = probe if kind == "fused" else (lambda: True)  # ("event": drained below)
                 e.stamp, e.log = dt.datetime.now(), (idx % ast["log_rate"] == 0) and log_on
                 e.post = e.info = None
@@ -670,9 +669,9 @@ class Solver:
                     npr = len(ast["pending"])
                     if npr > 0:
                         if len(pend) > depth and pend[0].ready is not None and not pend[0].ready():
-                            self._lag_records(min(npr, 2 * self._LAG_RECORDS))
+                            self._write_deferred(min(npr, 2 * self._LAG_RECORDS))
                         elif npr >= 4 * self._LAG_RECORDS:
-                            self._lag_records(self._LAG_RECORDS)
+                            self._write_deferred(self._LAG_RECORDS)
                 free = 1  # at most one ready check per launch beyond the forced ones: the device queue stays fed (a run
                 # of ready checks resolved back to back, e.g. after a host synchronisation, would leave it idle)
                 while pend and (drain > 0 or len(pend) > depth or (free > 0 and pend[0].ready is not None and pend[0].ready())):
@@ -683,7 +682,7 @@ class Solver:
                     stopped = c.resolve()
                     c.info = {**c.pre, **rel.info()}
                     if stopped:
-                        self._lag_end(c, rel, maxs, pend, prec)
+                        self._lag_end(c, plan, prec)
                         return
                     with ast["lock"]:
                         ast["pending"].append((c.idx, c.info, c.stamp, prec, c.log))
@@ -698,11 +697,13 @@ class Solver:
             ast.pop("lag", None)
             ast.pop("lag_logical", None)
             self._on_exception(err)
-        finally:
-            rel._window_stats = False
+        finally:  # what the loop configured on the criterion ends with it (steps() in pieces: the next loop asks again)
+            rel.want_window(False)
+            rel.lag_configure()
 
-    def _lag_records(self, k):
-        """Write the oldest k deferred records (flushing the log every _RECORD_LAG records)."""
+    def _write_deferred(self, k):
+        """Write the oldest k deferred history records / log lines: one structured array and one file write, the log
+        flushed every _RECORD_LAG lines (a reader of solver.log lags by at most one such batch)."""
         ast = self._astate
         with ast["lock"]:
             items = ast["pending"][:k]
@@ -711,42 +712,47 @@ class Solver:
             ast["unflushed"] = 0 if n >= self._RECORD_LAG else n
             self._record_batch(items, flush=n >= self._RECORD_LAG)
 
-    def _lag_end(self, c, rel, maxs, pend, prec):
-        """Check c said stop: drop the launches after it, restore its state, write its record, end the run."""
+    def _lag_rewind(self, plan, c, count_offset, x_ref):
+        """Back to check c of the lagged loop: the steps launched after it and every check still in flight are
+        dropped, the solver state and idx are c's, the MaxIter leaves count c.counts + count_offset, and the
+        RelError leaf compares its next check with `x_ref` (its value stays: the last resolved check's, as on the
+        synchronous path)."""
+        rel, maxs = plan
         ast = self._astate
-        undone = ast["idx"] - c.idx
-        pend.clear()
-        ast.pop("lag", None)
-        self._lag_restore(c.snap, undone)
+        ast.pop("lag_logical", None)
+        ast.pop("lag").clear()
+        self._lag_restore(c.snap, ast["idx"] - c.idx)
         ast["idx"] = c.idx
         for m, n in zip(maxs, c.counts):
-            m._i = n
-        ast.pop("lag_logical", None)
-        log_on = not ast.get("internal")
+            m.count = n + count_offset
+        _, val = rel.snapshot()
+        rel.restore((x_ref, val))
+
+    def _lag_end(self, c, plan, prec):
+        """Check c said stop: back to it as the synchronous path leaves it, write its record, end the run.  c has
+        run, so the RelError leaf keeps c's own iterate: what the check enqueued after c saw as its reference, or,
+        with none enqueued, what the leaf holds now."""
+        ast = self._astate
+        pend = ast["lag"]
+        kept, _ = pend[0].rel if pend else plan[0].snapshot()
+        self._lag_rewind(plan, c, 0, kept)
         with ast["lock"]:
             self._flush_records()
             self._record(c.idx, c.info, c.stamp, prec, c.log)
-        if log_on:
+        if not ast.get("internal"):
             ast["logger"].info(f"[{dt.datetime.now()}] Stopping Criterion satisfied -> END")
         self.writeback()
 
     def _lag_settle(self):
-        """steps() closed before the run ended: back to the state of its last item (the unresolved checks and
-        the steps launched after it dropped; their MaxIter counts and RelError reference undone)."""
+        """steps() closed before the run ended: back to the state of its last item, i.e. to the oldest unresolved
+        check before it ran."""
         ast = self._astate
-        ast.pop("lag_logical", None)
-        pend = ast.pop("lag", None)
         plan = self._lag_plan()
-        if not pend or plan is None:
-            return
-        rel, maxs = plan
-        k = pend[0]
-        self._lag_restore(k.snap, ast["idx"] - k.idx)
-        ast["idx"] = k.idx
-        for m, n in zip(maxs, k.counts):
-            m._i = n - 1
-        rel._x_prev = k.rel_prev
-        pend.clear()
+        if ast.get("lag") and plan is not None:
+            k = ast["lag"][0]
+            self._lag_rewind(plan, k, -1, k.rel[0])
+        ast.pop("lag", None)
+        ast.pop("lag_logical", None)
 
     # steps between an iteration and the write of its deferred history record / log line: records and log
     # lines are written in batches (one structured array and one file write per batch), also at stop_rate 1

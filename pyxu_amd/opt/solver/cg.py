@@ -10,10 +10,6 @@ from pyxu_amd.opt.solver._normal import normal_form_ex
 
 __all__ = ["CG"]
 
-# m_state key of row statistics a step has already computed for a state variable:
-# {var: (tensor, norm, host-readable row statistic)}, read by pyxu_amd.opt.stop.AbsError
-_ROWSTAT = "__rowstat__"
-
 
 # A p and the CG's <p, A p> partials from one set of launches when the operator can produce them
 # (pxa_dense_normal_pdot -> pxa_cg_update_tail; same bits either way).  Tests switch it off for the A/B.
@@ -142,7 +138,7 @@ class CG(pxa.Solver):
         ahead = _preset[3:] if _preset is not None and len(_preset) == 5 else None
         hr0 = ahead[0] if ahead else _HostRows(_dev.row_reduce(_dev.RED_SUMSQ, _rows2d(r)), self._hr_pool())
         self._rr = (hr0, r)  # ||r||^2 of the current residual (then carried from the previous step's beta)
-        mst[_ROWSTAT] = {"residual": (r, 2, hr0)}
+        mst.link.rowstat = {"residual": (r, 2, hr0)}
         self._Ap_next = None  # A p of the current p, launched ahead of the stop check (see m_step)
         if self._astate.get("internal"):
             self._Ap_next = ahead[1] if ahead else self._apply_p(mst["conjugate_dir"])
@@ -245,7 +241,7 @@ class CG(pxa.Solver):
         A p' while the host decides.  A p' of the last step is computed and dropped (no state changes)."""
         mst = self._mstate
         CG.steps_taken += 1
-        mst[_ROWSTAT] = {}
+        mst.link.rowstat = {}
         x, r, p = mst["x"], mst["residual"], mst["conjugate_dir"]
         Ap, self._Ap_next = self._Ap_next, None
         if Ap is None:
@@ -274,7 +270,7 @@ class CG(pxa.Solver):
             self._pap_ready = self._Ap_next
             hr = _KernelRows(hr[0], hr[1], seq)
             self._rr = (hr, r)
-            mst[_ROWSTAT] = {"residual": (r, 2, hr)}
+            mst.link.rowstat = {"residual": (r, 2, hr)}
             mst["x"], mst["residual"], mst["conjugate_dir"] = x, r, pn
             return
         if fast:
@@ -286,7 +282,7 @@ class CG(pxa.Solver):
             hr = _KernelRows(hr[0], hr[1], seq)
             self._rr = (hr, r)
             if internal:
-                mst[_ROWSTAT] = {"residual": (r, 2, hr)}
+                mst.link.rowstat = {"residual": (r, 2, hr)}
                 if not self._predicted_stop(rr_host):
                     self._Ap_next = self._apply_p(p)
             mst["x"], mst["residual"], mst["conjugate_dir"] = x, r, p
@@ -308,7 +304,7 @@ class CG(pxa.Solver):
             _dev.axpy_rows(beta, 1.0, _rows2d(p), _rows2d(r), out=_rows2d(p))  # p = r + beta p
             self._rr = (hr, r)
             if self._astate.get("internal"):
-                mst[_ROWSTAT] = {"residual": (r, 2, hr)}
+                mst.link.rowstat = {"residual": (r, 2, hr)}
                 if not self._predict_stop(rr_host):
                     self._Ap_next = self._apply_p(p)
         mst["x"], mst["residual"], mst["conjugate_dir"] = x, r, p

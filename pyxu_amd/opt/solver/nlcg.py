@@ -5,7 +5,7 @@ import pyxu_amd.abc as pxa
 import pyxu_amd.math.linesearch as ls
 import pyxu_amd.runtime as pxrt
 from pyxu_amd import _dev
-from pyxu_amd.opt.solver.cg import _ROWSTAT, _HostRows, _KernelRows
+from pyxu_amd.opt.solver.cg import _HostRows, _KernelRows
 
 __all__ = ["NLCG"]
 
@@ -90,7 +90,7 @@ class NLCG(pxa.Solver):
         # sum g0^2: the first beta's denominator and, published, the first stop check's statistic
         gg = _HostRows(_dev.row_reduce(_dev.RED_SUMSQ, _rows2d(g)))
         self._gg = (gg, g)
-        mst[_ROWSTAT] = {"gradient": (g, 2, gg)}
+        mst.link.rowstat = {"gradient": (g, 2, gg)}
         self._f_x = None  # (f(x) array, x) carried from the previous search
         self._gp = None  # (<g, p> partials, nb, g, p) left by the previous direction update
         self._ls_ws = None
@@ -129,7 +129,7 @@ class NLCG(pxa.Solver):
         self._f_x = (f_kp1, x_kp1)
         g_kp1 = self._f.grad(x_kp1)
         restart = self._astate["idx"] % mst["restart_rate"] == 0
-        mst[_ROWSTAT] = {}
+        mst.link.rowstat = {}
         if self._gg is not None and self._gg[1] is g_k:
             gg_k = self._gg[0].dev
         else:
@@ -147,7 +147,7 @@ class NLCG(pxa.Solver):
             hr = _HostRows(gg_kp1)  # async copy of sum g^2 for the stop check
             self._gp = None
         self._gg = (hr, g_kp1)
-        mst[_ROWSTAT] = {"gradient": (g_kp1, 2, hr)}
+        mst.link.rowstat = {"gradient": (g_kp1, 2, hr)}
         mst["x"], mst["gradient"], mst["conjugate_dir"], mst["ls_a_k"] = x_kp1, g_kp1, p_kp1, a_k
 
     def default_stop_crit(self):

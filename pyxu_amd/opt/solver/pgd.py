@@ -1,4 +1,5 @@
 """Proximal Gradient Descent (mirrors reference opt/solver/pgd.py:14-219)."""
+import collections
 import itertools
 import os
 import sys
@@ -8,6 +9,7 @@ import warnings
 import pyxu_amd.abc as pxa
 import pyxu_amd.runtime as pxrt
 from pyxu_amd import _dev
+from pyxu_amd.abc._stoplink import StepStats
 from pyxu_amd.opt.solver._fused import match_pgd_deblur
 from pyxu_amd.util import copy_if_unsafe
 
@@ -22,21 +24,42 @@ class AutoInferenceWarning(UserWarning):
 
 
 class _Momentum:
-    """The momentum sequence a_k (pgd.py:164-171) with `push`, which returns a consumed value (rollback of a
-    speculative step) without nesting one more itertools.chain per rollback."""
+    """The momentum sequence a_k (pgd.py:164-171).  It keeps the last `keep` values it returned, so that
+    `rewind(n)` makes the next n calls return the last n values again (steps undone by a stop check)."""
 
-    def __init__(self, it):
+    def __init__(self, it, keep=1):
         self._it = iter(it)
-        self._buf = []
+        self._kept = collections.deque(maxlen=keep)
+        self._again = []  # rewound values, the earliest last
 
     def __iter__(self):
         return self
 
     def __next__(self):
-        return self._buf.pop() if self._buf else next(self._it)
+        v = self._again.pop() if self._again else next(self._it)
+        self._kept.append(v)
+        return v
 
-    def push(self, v):
-        self._buf.append(v)
+    def rewind(self, n):
+        if n > len(self._kept):
+            raise ValueError(f"cannot rewind {n} momentum values: {len(self._kept)} kept.")
+        for _ in range(n):
+            self._again.append(self._kept.pop())
+
+
+def _has_relerr_on(crit, var):
+    """Whether the stop criterion `crit` holds a RelError on `var`."""
+    from pyxu_amd.abc.solver import _StoppingCriteriaComposition
+    from pyxu_amd.opt.stop import RelError
+
+    todo = [crit]
+    while todo:
+        c = todo.pop()
+        if isinstance(c, _StoppingCriteriaComposition):
+            todo += [c._lhs, c._rhs]
+        elif isinstance(c, RelError) and c._var == var:
+            return True
+    return False
 
 
 class PGD(pxa.Solver):
@@ -61,6 +84,16 @@ class PGD(pxa.Solver):
         from pyxu_amd.operator.linop import NullFunc
 
         mst = self._mstate
+        # everything a fit keeps outside the math state starts here (a run that raised or was abandoned leaves nothing)
+        self._spare = None  # a retired iterate that nothing else references: the next output buffer
+        self._pool = []  # retired iterates that something still references (the lagged engine's held states)
+        self._spec_refs = 0  # references the engine's rollback token holds to x_prev
+        self._x_check = None  # the x of the last stop check (RelError partials against it)
+        self._wpar_i = 0  # which of the two window-partials buffers the last launch wrote
+        self._wpub_pending = None  # (partials, flag buffer, seq) the next launch's extra workgroup publishes
+        # whether the run's stop criterion holds a RelError on x (the statistics the fused step's partials feed):
+        # without one, the check steps skip the partials (an extra read of x per launch)
+        self._rel_on_x = _has_relerr_on(self._astate.get("stop_crit"), "x")
         x0 = _dev.require(x0, "x0")
         mst["x"] = mst["x_prev"] = x0
         if self._f is None:
@@ -78,14 +111,15 @@ class PGD(pxa.Solver):
                 mst["tau"] = tau
             except Exception:
                 raise ValueError(f"tau must be positive, got {tau}.")
+        keep = max(self._LAG, 1) + 4  # the steps a stop check can undo: one (speculative), or those in flight (lagged)
         if acceleration:
             try:
                 assert d > 2
-                mst["a"] = _Momentum(pxrt.coerce(k / (k + 1 + d)) for k in itertools.count(start=0))
+                mst["a"] = _Momentum((pxrt.coerce(k / (k + 1 + d)) for k in itertools.count(start=0)), keep)
             except Exception:
                 raise ValueError(f"Expected d > 2, got {d}.")
         else:
-            mst["a"] = _Momentum(itertools.repeat(pxrt.coerce(0)))
+            mst["a"] = _Momentum(itertools.repeat(pxrt.coerce(0)), keep)
         self._plan = match_pgd_deblur(self._f, self._g, x0) if fused else None
         if self._plan is not None:
             p = self._plan
@@ -99,14 +133,12 @@ class PGD(pxa.Solver):
             ntiles = int(_dev.lib.pxa_pgd_tv2d_partials_count(p["stack"], p["n0"], p["n1"]))
             p["parts"] = _dev.empty_f64((2 * ntiles,), x0)
             p["tiles_per_row"] = ntiles // max(p["rows"], 1)
-            self._spare = None
-            self._x_check = None  # the x of the last stop check (RelError partials against it)
             # the solver never writes a tensor it has published as x (outputs go to fresh or recycled
             # buffers nobody else references), so stop criteria may keep references instead of copies
-            mst["__immutable__"] = frozenset({"x"})
+            mst.link.immutable = frozenset({"x"})
             # the step can compute the RelError statistics of the (x, x_prev) pair it reads (pxa_pgd_tv2d_plan_step_wfold):
             # offered to the criterion under the lagged engine, which resolves a check after the next step ran
-            mst["__window_ok__"] = True
+            mst.link.window_ok = True
 
     # publish the fused step's per-tile RelError partials to the stop criteria (False: A/B and parity tests)
     _fused_relerr = True
@@ -124,8 +156,8 @@ class PGD(pxa.Solver):
     def _spec_rollback(self, token):
         mst = self._mstate
         mst["x"], mst["x_prev"] = token
-        mst["a"].push(self._last_a)
-        mst.pop("__relerr__", None)
+        mst["a"].rewind(1)
+        mst.link.drop_offers()
         self._spare = None
         self._spec_refs = 0
 
@@ -140,8 +172,7 @@ class PGD(pxa.Solver):
     def _lag_flush(self):
         """Publish the window statistics still waiting for the next launch's extra workgroup (the run will not
         launch again): one fold launch."""
-        pend = getattr(self, "_wpub_pending", None)
-        self._wpub_pending = None
+        pend, self._wpub_pending = self._wpub_pending, None
         if pend is not None:
             p = self._plan
             _dev.tile_partials_publish(pend[0], p["rows"], p["tiles_per_row"], pend[1], pend[2])
@@ -153,150 +184,133 @@ class PGD(pxa.Solver):
     def _lag_restore(self, snap, undone):
         mst = self._mstate
         mst["x"], mst["x_prev"] = snap
-        hist = list(getattr(self, "_a_hist", ()))
-        for v in reversed(hist[len(hist) - undone:] if undone > 0 else []):  # next() returns the earliest first
-            mst["a"].push(v)
-        mst.pop("__relerr__", None)
-        mst.pop("__relerr_sink__", None)
-        mst.pop("__relerr_window__", None)
+        mst["a"].rewind(undone)
+        mst.link.drop_offers()
         self._wpub_pending = None
         self._spare = None
         self._x_check = None
-        self.__dict__.pop("_pool", None)
+        self._pool = []
 
-    # Output buffers under the lagged engine: the held check states keep the old x_prev referenced, so the refcount
-    # recycling below never finds it free and every step would allocate (torch.empty_like: several us of host time
-    # per step at stop_rate 1, where the host sets the pace).  Retired iterates wait in a small pool instead and are
-    # reused once nothing references them (the same refcount + storage test: a held state, a steps() item or a user
-    # view keeps a buffer out of reuse).
+    # Output buffers.  The old x_prev becomes the next output buffer iff nobody else holds it (the reference allocates
+    # fresh arrays, so user-held results must never be overwritten): its Python reference count and its storage's use
+    # count say so.  Under the lagged engine the held check states keep it referenced, and every step would allocate
+    # (torch.empty_like: several us of host time per step at stop_rate 1, where the host sets the pace): there, the
+    # iterates the window steps retire wait in a small pool and are reused once nothing references them (the same
+    # test: a held state, a steps() item or a user view keeps a buffer out of reuse).
     _POOL_MAX = 16
 
-    def _pool_take(self, x, xp):
-        pool = self.__dict__.get("_pool")
-        if pool:
-            for i in range(len(pool)):
-                b = pool[i]
-                # references: the pool's, b, getrefcount's argument
-                if (sys.getrefcount(b) == 3 and b is not x and b is not xp and b.shape == x.shape and b.dtype == x.dtype
-                        and _dev.storage_exclusive(b)):
-                    del pool[i]
-                    return b
+    def _take(self, x, xp):
+        """An output buffer for the step from (x, xp)."""
+        out = self._spare
+        if out is not None and out is not x and out is not xp:
+            return out
+        pool = self._pool
+        for i in range(len(pool)):
+            b = pool[i]
+            # references: the pool's, b, getrefcount's argument
+            if (sys.getrefcount(b) == 3 and b is not x and b is not xp and b.shape == x.shape and b.dtype == x.dtype
+                    and _dev.storage_exclusive(b)):
+                del pool[i]
+                return b
         return _dev.empty_like(x)
 
-    def _pool_put(self, b):
-        if self._astate.get("lag") is None:  # (only while the lagged engine runs; emptied when it ends)
-            self.__dict__.pop("_pool", None)
+    def _retire(self, xp, x, held, pool=False):
+        """xp has just left the state (x is the new x_prev): the next output buffer iff nobody else holds it.  `held`
+        is sys.getrefcount(xp) as the step took it with xp in one local of its own (2: that local and getrefcount's
+        argument, plus what the engine's rollback token holds).  With `pool`, a buffer still held waits in the pool."""
+        free = held == 2 + self._spec_refs
+        self._spec_refs = 0
+        if free and xp.data_ptr() != x.data_ptr() and _dev.storage_exclusive(xp):
+            self._spare = xp
             return
-        pool = self.__dict__.setdefault("_pool", [])
-        pool.append(b)
+        self._spare = None
+        if not pool:
+            return
+        pool = self._pool
+        if self._astate.get("lag") is None:  # (a pool only while the lagged engine runs; emptied when it ends)
+            pool.clear()
+            return
+        pool.append(xp)
         if len(pool) > self._POOL_MAX:
             del pool[0]
-
-    def _rel_on_x(self):
-        """Whether the run's stop criterion holds a RelError on x (the statistics the fused step's partials feed):
-        without one, the check steps skip the partials (an extra read of x per launch)."""
-        crit = self._astate.get("stop_crit")
-        key = id(crit)
-        cached = self.__dict__.get("_rel_on_x_cache")
-        if cached is not None and cached[0] == key and cached[1] is crit:
-            return cached[2]
-        from pyxu_amd.abc.solver import _StoppingCriteriaComposition
-        from pyxu_amd.opt.stop import RelError
-
-        todo, found = [crit], False
-        while todo:
-            c = todo.pop()
-            if isinstance(c, _StoppingCriteriaComposition):
-                todo += [c._lhs, c._rhs]
-            elif isinstance(c, RelError) and c._var == "x":
-                found = True
-        self._rel_on_x_cache = (key, crit, found)
-        return found
 
     def m_step(self):
         mst = self._mstate
         a = next(mst["a"])
-        self._last_a = a
-        ah = self.__dict__.get("_a_hist")
-        if ah is None:
-            import collections
-
-            ah = self._a_hist = collections.deque(maxlen=256)
-        ah.append(a)
-        if self._plan is not None:
-            p = self._plan
-            mst.pop("__relerr__", None)  # (holds x_prev: drop it before the buffer-recycling refcount below)
-            x, xp = mst["x"], mst["x_prev"]
-            out = self._spare
-            if out is None or out is x or out is xp:
-                out = self._pool_take(x, xp)
-            tau = mst["tau"]
-            wnd = mst.pop("__relerr_window__", None)
-            if wnd is not None:
-                # (lagged engine) this launch computes the statistics of the check before it from its window loads,
-                # and an extra workgroup of it publishes those of the check before that (two partials buffers,
-                # alternately): no fold launch (PXA_LAG_PUB=0: a fold launch behind the step instead)
-                if self._LAG_PUB:
-                    wp = p.get("wparts")
-                    if wp is None:
-                        wp = p["wparts"] = (p["parts"], _dev.empty_f64(p["parts"].shape, x))
-                    self._wpar_i = getattr(self, "_wpar_i", 0) ^ 1
-                    cur = wp[self._wpar_i]
-                    p["plan"].step_wpub(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], cur,
-                                        getattr(self, "_wpub_pending", None))
-                    self._wpub_pending = (cur, wnd[0], wnd[1])
-                else:
-                    p["plan"].step_window(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], p["parts"], wnd[0], wnd[1])
-                mst["x_prev"], mst["x"] = x, out
-                refs = 2 + getattr(self, "_spec_refs", 0)
-                self._spec_refs = 0
-                self._spare = xp if (sys.getrefcount(xp) == refs and xp.data_ptr() != x.data_ptr()
-                                     and _dev.storage_exclusive(xp)) else None
-                if self._spare is None:
-                    self._pool_put(xp)
-                return
-            # RelError partials only for the launch right before a stop check (the engine advances idx
-            # before m_step: the next check runs at idx when idx % stop_rate == 0).  RelError compares with
-            # the iterate of the PREVIOUS check (opt/stop.py:353-382), which the criterion keeps: x itself at
-            # stop_rate 1, else the x this solver saw at that check (self._x_check, the same tensor object)
-            ast = self._astate
-            sr = ast.get("stop_rate")
-            if sr is not None and (ast["idx"] - 1) % sr == 0:
-                self._x_check = x  # a check ran right before this step, on this x
-            want = self._fused_relerr and sr is not None and ast["idx"] % sr == 0 and self._rel_on_x()
-            parts = p["parts"] if want else None
-            xref = self._x_check if want else None
-            if xref is None:
-                xref = x
-            # the stop criterion's host buffer for this launch's folded statistics, if it offered one
-            sink = mst.pop("__relerr_sink__", None) if want else None
-            in_kernel = sink is not None and sink[0] == "x" and len(sink) > 2 and bool(sink[2])
-            sink = sink[1] if sink is not None and sink[0] == "x" else None
-            # the fold: in the launch's last workgroup (PXA_RELERR_SINK=1), else a fold launch right behind it,
-            # enqueued by the same C call (a side stream for it, so that it ran beside the next launch, cost more
-            # host time in the event record / wait than it saved: r05s)
-            seq = sink.next_seq() if sink is not None else 0
-            p["plan"].step(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], partials=parts,
-                           x_ref=None if xref is x else xref, sink=sink, seq=seq,
-                           fold_launch=sink is not None and not in_kernel)
-            if want:  # (var, x_new, the x the statistics are relative to, partials, rows, tiles per row, folded)
-                mst["__relerr__"] = ("x", out, xref, parts, p["rows"], p["tiles_per_row"],
-                                     (sink, seq) if sink is not None else None)
-            else:
-                mst.pop("__relerr__", None)
-            mst["x_prev"], mst["x"] = x, out
-            # recycle the old x_prev as the next output buffer iff nobody else holds it (the reference
-            # allocates fresh arrays, so user-held results must never be overwritten)
-            refs = 2 + getattr(self, "_spec_refs", 0)
-            self._spec_refs = 0
-            self._spare = xp if (sys.getrefcount(xp) == refs and xp.data_ptr() != x.data_ptr()
-                                 and _dev.storage_exclusive(xp)) else None
+        if self._plan is None:
+            # generic path: y = (x - x_prev) * a + x ; z = y - tau * grad(y) ; x+ = prox_g(z, tau)
+            y = _dev.extrapolate(a, mst["x"], mst["x_prev"])
+            z = copy_if_unsafe(self._f.grad(y))
+            z = _dev.axpby(-mst["tau"], z, 1.0, y, out=z)
+            mst["x_prev"], mst["x"] = mst["x"], self._g.prox(z, mst["tau"])
             return
-        # generic path: y = (x - x_prev) * a + x ; z = y - tau * grad(y) ; x+ = prox_g(z, tau)
-        y = _dev.extrapolate(a, mst["x"], mst["x_prev"])
-        z = copy_if_unsafe(self._f.grad(y))
-        z = _dev.axpby(-mst["tau"], z, 1.0, y, out=z)
-        mst["x_prev"], mst["x"] = mst["x"], self._g.prox(z, mst["tau"])
+        link = mst.link
+        link.step_stats = None  # (holds x_prev: dropped before the buffer-recycling reference count)
+        wnd = link.window
+        if wnd is not None:
+            link.window = None
+            self._step_window(a, wnd)
+        else:
+            self._step_epilogue(a, link)
+
+    def _step_window(self, a, wnd):
+        """(lagged engine) This launch computes the statistics of the check before it from its window loads, and an
+        extra workgroup of it publishes those of the check before that (two partials buffers, alternately): no
+        fold launch (PXA_LAG_PUB=0: a fold launch behind the step instead)."""
+        mst, p = self._mstate, self._plan
+        x, xp = mst["x"], mst["x_prev"]
+        out = self._take(x, xp)
+        tau = mst["tau"]
+        if self._LAG_PUB:
+            wp = p.get("wparts")
+            if wp is None:
+                wp = p["wparts"] = (p["parts"], _dev.empty_f64(p["parts"].shape, x))
+            self._wpar_i ^= 1
+            cur = wp[self._wpar_i]
+            p["plan"].step_wpub(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], cur, self._wpub_pending)
+            self._wpub_pending = (cur, wnd.buffer, wnd.seq)
+        else:
+            p["plan"].step_window(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], p["parts"], wnd.buffer, wnd.seq)
+        mst["x_prev"], mst["x"] = x, out
+        held = sys.getrefcount(xp)
+        self._retire(xp, x, held, pool=True)
+
+    def _step_epilogue(self, a, link):
+        """The launch right before a stop check also computes that check's RelError partials in its epilogue (the
+        engine advances idx before m_step: the next check runs at idx when idx % stop_rate == 0).  RelError
+        compares with the iterate of the PREVIOUS check (opt/stop.py:353-382), which the criterion keeps: x itself
+        at stop_rate 1, else the x this solver saw at that check (self._x_check, the same tensor object)."""
+        mst, p, ast = self._mstate, self._plan, self._astate
+        x, xp = mst["x"], mst["x_prev"]
+        out = self._take(x, xp)
+        tau = mst["tau"]
+        sr = ast.get("stop_rate")
+        if sr is not None and (ast["idx"] - 1) % sr == 0:
+            self._x_check = x  # a check ran right before this step, on this x
+        want = self._fused_relerr and sr is not None and ast["idx"] % sr == 0 and self._rel_on_x
+        parts = xref = sink = None
+        if want:
+            parts, xref = p["parts"], self._x_check
+            # the stop criterion's host buffer for this launch's folded statistics, if it offered one
+            sink, link.sink = link.sink, None
+            if sink is not None and sink.var != "x":
+                sink = None
+        if xref is None:
+            xref = x
+        # the fold: in the launch's last workgroup (PXA_RELERR_SINK=1), else a fold launch right behind it,
+        # enqueued by the same C call (a side stream for it, so that it ran beside the next launch, cost more
+        # host time in the event record / wait than it saved: r05s)
+        buf = sink.buffer if sink is not None else None
+        seq = buf.next_seq() if buf is not None else 0
+        p["plan"].step(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], partials=parts,
+                       x_ref=None if xref is x else xref, sink=buf, seq=seq,
+                       fold_launch=buf is not None and not sink.in_kernel)
+        if want:
+            link.step_stats = StepStats("x", out, xref, parts, p["rows"], p["tiles_per_row"],
+                                        (buf, seq) if buf is not None else None)
+        mst["x_prev"], mst["x"] = x, out
+        held = sys.getrefcount(xp)
+        self._retire(xp, x, held)
 
     def default_stop_crit(self):
         from pyxu_amd.opt.stop import RelError

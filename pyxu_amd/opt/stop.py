@@ -13,6 +13,7 @@ import numpy as np
 
 import pyxu_amd.abc as pxa
 from pyxu_amd import _dev
+from pyxu_amd.abc._stoplink import FlagRing, Sink, Window, link_of
 
 __all__ = ["MaxIter", "ManualStop", "MaxDuration", "Memorize", "AbsError", "RelError"]
 
@@ -83,6 +84,19 @@ class MaxIter(pxa.StoppingCriterion):
 
     def clear(self):
         self._i = 0
+
+    @property
+    def count(self):
+        """Checks made so far (settable: an engine that drops checks it enqueued ahead takes them back)."""
+        return self._i
+
+    @count.setter
+    def count(self, i):
+        self._i = int(i)
+
+    def fires_next(self) -> bool:
+        """Whether the next stop() returns True."""
+        return self._i + 1 > self._n
 
 
 class ManualStop(pxa.StoppingCriterion):
@@ -195,7 +209,8 @@ class AbsError(pxa.StoppingCriterion):
         # a row statistic the solver step already computed for this very array (CG publishes
         # ||r||^2 of its residual: the same pxa_row_reduce, hence the same bits) saves a reduction and
         # a host sync on the whole device queue
-        pre = state.get("__rowstat__", {}).get(self._var) if hasattr(state, "get") else None
+        link = link_of(state)
+        pre = link.rowstat.get(self._var) if link is not None else None
         if pre is not None and pre[0] is x and pre[1] == self._norm and self._f is _identity and self._reduce is None:
             st = np.asarray(pre[2].host(), dtype=np.float64)
             self._val = _finish(st, self._norm).reshape(*x.shape[:-1], 1)
@@ -237,25 +252,55 @@ class RelError(pxa.StoppingCriterion):
         except Exception:
             raise ValueError(f"norm: expected non-negative, got {norm}.")
         self._satisfy_all = satisfy_all
+        self._flags = self._async_buf = None  # host buffers of stop_async, reused across checks and runs
+        self.clear()
+
+    def clear(self):
         self._val = np.r_[0]
         self._x_prev = None
+        self._lag = None  # lag_configure
+        self._window_stats = False  # want_window
+        #: (kind, ready) of the last stop_async: "sync" (decided at once, ready None), "fused" (statistics published
+        #: into a flag buffer of their own; ready() polls them) or "event" (one shared buffer: resolve it before the
+        #: next check is issued; ready() queries its event)
+        self.last_async = ("sync", None)
 
-    def _keep(self, state, x):
+    def lag_configure(self, nbufs=None, in_kernel_fold=None):
+        """While it keeps several checks unresolved, an engine needs `nbufs` flag buffers (the checks in flight, the
+        one being resolved, the next launch's) and chooses the fold (`_in_kernel_fold`) itself.  No arguments: back
+        to the defaults (as clear() does)."""
+        self._lag = None if nbufs is None else (max(2, int(nbufs)), bool(in_kernel_fold))
+
+    def want_window(self, on):
+        """Whether the next stop_async may leave its statistics to the step launched after it (StopLink.window):
+        only an engine that resolves the check after that step has run can ask for this."""
+        self._window_stats = bool(on)
+
+    def snapshot(self):
+        return self._x_prev, self._val
+
+    def restore(self, s):
+        self._x_prev, self._val = s
+
+    def _ring(self, rows):
+        nbufs = self._lag[0] if self._lag is not None else 2  # this check's buffer and the next launch's
+        self._flags = FlagRing.matching(self._flags, rows, nbufs)
+        return self._flags
+
+    def _keep(self, link, x):
         """What the criterion keeps of x for its next check: a reference when the solver promises never
-        to write a tensor it has published under this name (state["__immutable__"]), else a copy."""
-        if hasattr(state, "get") and self._var in state.get("__immutable__", ()):
+        to write a tensor it has published under this name (StopLink.immutable), else a copy."""
+        if link is not None and self._var in link.immutable:
             return x
         return _dev.copy(x)
 
-    def _fused(self, state, x):
-        """The solver step's own statistics for this check, or None: the fused PGD step publishes
-        (var, x_new, x, per-tile partials, rows, tiles per row) when its launch computed
-        sum (x_new - x)^2 and sum x^2 per tile; they are this check's statistics iff x_new is the state
-        x and x is the very tensor this criterion kept at its previous check (stop_rate 1, or any rate
-        whose previous check saw the launch's input)."""
-        h = state.get("__relerr__") if hasattr(state, "get") else None
-        if (h is None or h[0] != self._var or h[1] is not x or self._x_prev is not h[2] or self._f is not _identity
-                or self._norm != 2):
+    def _fused(self, link, x):
+        """The solver step's own statistics for this check (StopLink.step_stats), or None: they are this check's
+        iff x_new is the state x and x_ref is the very tensor this criterion kept at its previous check
+        (stop_rate 1, or any rate whose previous check saw the launch's input)."""
+        h = link.step_stats if link is not None else None
+        if (h is None or h.var != self._var or h.x_new is not x or self._x_prev is not h.x_ref
+                or self._f is not _identity or self._norm != 2):
             return None
         return h
 
@@ -283,14 +328,15 @@ class RelError(pxa.StoppingCriterion):
         x = state[self._var]
         if isinstance(x, numbers.Real):
             raise NotImplementedError("pyxu_amd: RelError on scalar state variables is not supported.")
+        link = link_of(state)
         if self._x_prev is None:
-            self._x_prev = self._keep(state, x)
+            self._x_prev = self._keep(link, x)
             self._val = np.zeros(shape=(1,) if (x.ndim == 1) else tuple(x.shape[:-1]))
             return False
-        h = self._fused(state, x)
+        h = self._fused(link, x)
         if h is not None:
-            st = _dev.empty_f64((2, max(h[4], 1)), x)
-            _dev.tile_partials_fold(h[3], h[4], h[5], st)
+            st = _dev.empty_f64((2, max(h.rows, 1)), x)
+            _dev.tile_partials_fold(h.partials, h.rows, h.tiles_per_row, st)
             if self._reduce is not None:
                 st = self._reduce(st, "sum")
             self._x_prev = x
@@ -303,7 +349,7 @@ class RelError(pxa.StoppingCriterion):
         # the reference copies x after the decision (stop.py:381); the copy is decision-independent, so it
         # is made here, before the host sync.  Identity f and the 2-norm (the default): both statistics
         # and the copy in one pass over x and x_prev (pxa_relerr_stats).
-        borrow = hasattr(state, "get") and self._var in state.get("__immutable__", ())
+        borrow = link is not None and self._var in link.immutable
         if self._f is _identity and self._norm == 2 and 0 < rows <= 65535 and fx.dtype == fx_prev.dtype:
             x_copy = _dev.relerr_stats(fx, fx_prev, st, copy=not borrow)
         else:
@@ -318,7 +364,7 @@ class RelError(pxa.StoppingCriterion):
 
     # hook: combine a device row statistic across shards (identity on one process)
     _reduce = None
-    # Offer the fused PGD step a host buffer to fold its statistics into ("__relerr_sink__" of the solver state):
+    # Offer the fused PGD step a host buffer to fold its statistics into (the sink of the solver state's StopLink):
     # the step then launches the fold right behind its own launch, instead of this criterion launching it at the
     # next check, after the host's decision on the previous one -- at stop_rate 1 that put a host hop between
     # every step and its fold (r05q: 36 us per step, the device idle ~9 us of it).  PXA_RELERR_SINK=1 folds in
@@ -332,7 +378,7 @@ class RelError(pxa.StoppingCriterion):
         copy of x are enqueued now; the returned callable waits for them only and decides.  Same
         kernels, same bits, same decision, same info() as stop()."""
         x = state[self._var]
-        self._last_async = ("sync", None)  # (kind, readiness probe) of this check's statistics: the lagged engine
+        self.last_async = ("sync", None)
         if (isinstance(x, numbers.Real) or self._x_prev is None or self._reduce is not None
                 or self._f is not _identity or self._norm != 2):
             return super().stop_async(state)
@@ -341,19 +387,13 @@ class RelError(pxa.StoppingCriterion):
         rows = x.numel() // x.shape[-1]
         if not (0 < rows <= 65535 and x.dtype == self._x_prev.dtype):
             return super().stop_async(state)
-        if (getattr(self, "_window_stats", False) and hasattr(state, "__setitem__") and state.get("__window_ok__")
-                and state.get("x_prev") is self._x_prev):
+        link = link_of(state)
+        if self._window_stats and link is not None and link.window_ok and state.get("x_prev") is self._x_prev:
             # (the solver's lagged engine) the NEXT step computes this check's statistics from the (x, x_prev) pair
             # it reads anyway and folds them into a ring buffer: this check is resolved after that step has run
-            nb = max(2, int(getattr(self, "_nbufs", 2)))
-            bufs = getattr(self, "_flag_bufs", None)
-            if bufs is None or bufs[0].rows != rows or len(bufs) != nb:
-                bufs = self._flag_bufs = tuple(_dev.HostFlagBuffer(rows) for _ in range(nb))
-            self._win_i = (getattr(self, "_win_i", -1) + 1) % nb
-            fb = bufs[self._win_i]
+            fb = self._ring(rows).take()
             seq = fb.next_seq()
-            state["__relerr_window__"] = (fb, seq)
-            state.pop("__relerr_sink__", None)
+            link.window, link.sink = Window(fb, seq), None
             self._x_prev = x
             shape = x.shape[:-1]
 
@@ -368,31 +408,24 @@ class RelError(pxa.StoppingCriterion):
                     fb.wait(seq)
                     return self._decide(_finish(fb.stats.copy(), self._norm), shape)
 
-            self._last_async = ("fused", lambda: fb.landed(seq))
+            self.last_async = ("fused", lambda: fb.landed(seq))
             return resolve_window
-        h = self._fused(state, x)
+        h = self._fused(link, x)
         if h is not None:
             # the step's own per-tile partials, folded straight into coherent host memory with a completion flag
             # per statistic: no pass over x / x_prev, no copy, no stream event.  x is kept (a reference) now, so
             # that the solver's next step, enqueued before the decision is read, may recycle the previous
-            # iterate's buffer.  Two buffers, alternately: this check reads one while the launch behind it
-            # (enqueued before the decision) may fold into the other -- the solver finds that one as the
-            # "__relerr_sink__" of its state, and then the fold is part of its launch (h[6] = (buffer, seq))
-            # a ring of _nbufs buffers (2: this check's and the next launch's; the solver's lagged engine keeps
-            # several checks unresolved and asks for more, abc/solver.py _lag_loop)
-            nb = max(2, int(getattr(self, "_nbufs", 2)))
-            bufs = getattr(self, "_flag_bufs", None)
-            if bufs is None or bufs[0].rows != rows or len(bufs) != nb:
-                bufs = self._flag_bufs = tuple(_dev.HostFlagBuffer(rows) for _ in range(nb))
-            folded = h[6] if len(h) > 6 else None
-            if folded is not None and any(folded[0] is b for b in bufs):
-                fb, seq = folded
+            # iterate's buffer.  A ring of buffers (2, or what lag_configure asked for): this check reads one while
+            # the launch behind it (enqueued before the decision) may fold into the next -- the solver finds that one
+            # as the StopLink's sink, and then the fold is part of its launch (StepStats.folded)
+            ring = self._ring(rows)
+            if h.folded is not None and ring.owns(h.folded[0]):
+                fb, seq = h.folded
             else:
-                fb = bufs[0]
-                seq = fb.fold(h[3], h[5])
-            if self._offer_sink and hasattr(state, "__setitem__"):
-                nxt = bufs[(next(i for i, b in enumerate(bufs) if b is fb) + 1) % nb]
-                state["__relerr_sink__"] = (self._var, nxt, self._in_kernel_fold)
+                fb = ring.bufs[0]
+                seq = fb.fold(h.partials, h.tiles_per_row)
+            if self._offer_sink:
+                link.sink = Sink(self._var, ring.after(fb), self._lag[1] if self._lag is not None else self._in_kernel_fold)
             self._x_prev = x
             shape = x.shape[:-1]
 
@@ -400,24 +433,24 @@ class RelError(pxa.StoppingCriterion):
                 fb.wait(seq)
                 return self._decide(_finish(fb.stats.copy(), self._norm), shape)  # (2, rows) view
 
-            self._last_async = ("fused", lambda: fb.landed(seq))
+            self.last_async = ("fused", lambda: fb.landed(seq))
             return resolve_flags
         # one device / pinned-host statistics pair and one event per criterion, reused: a check is
         # resolved before the next one is issued
-        buf = getattr(self, "_async_buf", None)
+        buf = self._async_buf
         if buf is None or buf[0].shape[1] != rows:
             buf = (torch.empty((2, rows), dtype=torch.float64, pin_memory=True), torch.cuda.Event())
             self._async_buf = buf
         host, ev = buf
         # the final fold writes the statistics straight into the pinned host buffer (device-mapped): no device ->
         # host copy launch between the statistics and the event
-        borrow = self._var in state.get("__immutable__", ()) if hasattr(state, "get") else False
+        borrow = link is not None and self._var in link.immutable
         x_copy = _dev.relerr_stats(x, self._x_prev, host, copy=not borrow)
         if borrow:
             x_copy = x
         _dev.record_event(ev)
         shape = x.shape[:-1]
-        self._last_async = ("event", ev.query)  # (one buffer: resolved before the next check is issued)
+        self.last_async = ("event", ev.query)
 
         def resolve():
             _dev.wait_event(ev)
@@ -431,7 +464,3 @@ class RelError(pxa.StoppingCriterion):
         if self._val.size == 1:
             return {f"RelError[{self._var}]": float(self._val.item())}
         return {f"RelError[{self._var}]_min": float(self._val.min()), f"RelError[{self._var}]_max": float(self._val.max())}
-
-    def clear(self):
-        self._val = np.r_[0]
-        self._x_prev = None

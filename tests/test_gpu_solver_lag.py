@@ -5,7 +5,9 @@ the synchronous reference order (solver.py:588-663, stop.py:353-382) on the same
 the same iterate bit for bit, the same history records (MaxIter counts checks), the same steps() items, also when
 steps() is consumed in pieces, and the same log lines.  With the default window statistics (the next step's
 (x, x_prev) loads: the same sums in another order) the RelError values agree to 1e-12 relative instead of bit for
-bit; with the epilogue statistics they are bit-identical.
+bit; with the epilogue statistics they are bit-identical.  The criterion ends as on the synchronous path too (info()
+is the last history record, the RelError leaf keeps the solution tensor), and nothing of a run survives it: the same
+solver and criterion objects fitted again, or the criterion reused elsewhere, give a fresh object's result.
 """
 import re
 
@@ -55,33 +57,56 @@ def _problem(sh=(96, 128), stack=1, entry=None):
     return f, pxo.PositiveOrthant(dim=stack * N), stack * N
 
 
-def _run(lagged, crit_fn, mode, monkeypatch, tmp_path, tag, depth=8, inkernel=False, pieces=None, stack=1, window=True,
-         pub=True, entry=None):
+def _rel_leaf(crit):
+    if isinstance(crit, pxst.RelError):
+        return crit
+    for side in ("_lhs", "_rhs"):
+        leaf = _rel_leaf(getattr(crit, side)) if hasattr(crit, side) else None
+        if leaf is not None:
+            return leaf
+    return None
+
+
+def _engine(lagged, monkeypatch, depth=8, inkernel=False, window=True, pub=True):
     monkeypatch.setattr(pxa.Solver, "_LAG", depth if lagged else 0)
     monkeypatch.setattr(pxa.Solver, "_LAG_INKERNEL", inkernel)
     monkeypatch.setattr(pxa.Solver, "_LAG_WINDOW", window)
     monkeypatch.setattr(pxs.PGD, "_LAG_PUB", pub)
     if not lagged:  # the synchronous reference order itself (no speculative checks either)
         monkeypatch.setattr(pxs.PGD, "_spec_supported", lambda self: False)
-    monkeypatch.setattr(pxa.Solver, "_LAG_INKERNEL", inkernel)
+
+
+def _collect(s, crit, folder, items=(), stats_eq=True):
+    """What a finished fit left: the result, the history, the log, and the criterion's end state (`end`: its info(),
+    the last history row cast back from it, and whether the RelError leaf keeps the solution tensor itself)."""
+    data, hist = s.stats()
+    log = (folder / "solver.log").read_text()
+    log = re.sub(r"\[[0-9: .-]+\]", "[t]", log)  # time stamps differ
+    info = crit.info()
+    end = dict(info=info, keeps_x=_rel_leaf(crit).snapshot()[0].data_ptr() == data["x"].data_ptr(),
+               is_last_row=all(np.asarray(v, dtype=hist.dtype[k]) == hist[k][-1] for k, v in info.items()))
+    return dict(x=to_NUMPY(data["x"]), idx=s._astate["idx"], a=next(s._mstate["a"]), items=list(items), stats_eq=stats_eq,
+                hist={k: np.asarray(hist[k]) for k in hist.dtype.names}, log=log, end=end)
+
+
+def _run(lagged, crit_fn, mode, monkeypatch, tmp_path, tag, depth=8, inkernel=False, pieces=None, stack=1, window=True,
+         pub=True, entry=None):
+    _engine(lagged, monkeypatch, depth, inkernel, window, pub)
     with pxrt.Precision(pxrt.Width.SINGLE):
         f, g, N = _problem(stack=stack, entry=entry)
         s = pxs.PGD(f=f, g=g, show_progress=False, stop_rate=1, folder=tmp_path / tag)
         x0 = to_device(np.zeros(N, np.float32))
         items, stats_eq = [], True
+        crit = crit_fn()
         if mode == "BLOCK":
-            s.fit(x0=x0, stop_crit=crit_fn())
+            s.fit(x0=x0, stop_crit=crit)
         else:
-            s.fit(x0=x0, stop_crit=crit_fn(), mode=pxa.Mode.MANUAL)
+            s.fit(x0=x0, stop_crit=crit, mode=pxa.Mode.MANUAL)
             for n in (pieces or [None]):
                 for it in s.steps(n):
                     items.append(to_NUMPY(it["x"]))
                     stats_eq &= bool(torch.equal(s.stats()[0]["x"], it["x"]))  # stats() between items: that item
-        data, hist = s.stats()
-        log = (tmp_path / tag / "solver.log").read_text()
-        log = re.sub(r"\[[0-9: .-]+\]", "[t]", log)  # time stamps differ
-        return dict(x=to_NUMPY(data["x"]), idx=s._astate["idx"], a=next(s._mstate["a"]), items=items, stats_eq=stats_eq,
-                    hist={k: np.asarray(hist[k]) for k in hist.dtype.names}, log=log)
+        return _collect(s, crit, tmp_path / tag, items, stats_eq)
 
 
 def _same(a, b, exact_rel=True, items=True):
@@ -90,6 +115,13 @@ def _same(a, b, exact_rel=True, items=True):
     significant digits; everything else bit for bit."""
     assert a["idx"] == b["idx"] and a["a"] == b["a"]
     assert np.array_equal(a["x"], b["x"])
+    # the criterion's end state: info() is the run's last history row, the same in both runs
+    assert a["end"]["is_last_row"] and b["end"]["is_last_row"] and set(a["end"]["info"]) == set(b["end"]["info"])
+    for k, v in b["end"]["info"].items():
+        if k.startswith("RelError") and not exact_rel:
+            np.testing.assert_allclose(a["end"]["info"][k], v, rtol=1e-12, atol=0, err_msg=k)
+        else:
+            assert a["end"]["info"][k] == v, k
     assert set(a["hist"]) == set(b["hist"])
     for k in b["hist"]:
         if k.startswith("RelError") and not exact_rel:
@@ -121,6 +153,9 @@ def test_lagged_checks_match_synchronous_relerr_stop(mode, stats, monkeypatch, t
     assert 20 < b["idx"] < 500
     _same(a, b, exact_rel=not stats.startswith("window"))
     assert a["stats_eq"]
+    # after the stop both engines leave the RelError leaf with the stopping check's x: the solution tensor itself
+    assert a["end"]["keeps_x"] and b["end"]["keeps_x"]
+    assert a["end"]["info"]["N_iter"] == b["idx"] + 1
 
 
 @pytest.mark.parametrize("depth", [1, 3, 16])
@@ -152,3 +187,53 @@ def test_lagged_steps_consumed_in_pieces(monkeypatch, tmp_path):
     a = _run(True, crit, "MANUAL", monkeypatch, tmp_path, "lag", pieces=[5, 1, 17, None])
     b = _run(False, crit, "MANUAL", monkeypatch, tmp_path, "sync")
     _same(a, b, exact_rel=False)
+
+
+def _fit(s, crit, N, mode=pxa.Mode.BLOCK):
+    s.fit(x0=to_device(np.zeros(N, np.float32)), stop_crit=crit, mode=mode)
+
+
+@pytest.mark.parametrize("first", ["stopped", "abandoned"])
+@pytest.mark.parametrize("window", [True, False], ids=["window", "epilogue"])
+def test_refit_with_the_same_solver_and_criterion(first, window, monkeypatch, tmp_path):
+    """One solver object and one criterion object fitted twice under the lagged engine give, the second time, the
+    first fit's result and a fresh solver's: nothing of a run survives into the next.  The first run is stopped by
+    RelError (launches in flight are dropped), or abandoned: MANUAL mode, steps(5) consumed and closed."""
+    new_crit = lambda: pxst.MaxIter(500) | pxst.RelError(eps=3e-3)  # noqa: E731
+    fresh = _run(True, new_crit, "BLOCK", monkeypatch, tmp_path, "fresh", window=window)
+    with pxrt.Precision(pxrt.Width.SINGLE):
+        f, g, N = _problem()
+        s = pxs.PGD(f=f, g=g, show_progress=False, stop_rate=1, folder=tmp_path / "twice")
+        crit = new_crit()
+        if first == "stopped":
+            _fit(s, crit, N)
+            one = _collect(s, crit, tmp_path / "twice")
+            assert 20 < one["idx"] < 500
+            _same(one, fresh, exact_rel=not window)
+        else:
+            _fit(s, crit, N, pxa.Mode.MANUAL)
+            assert len([it for it in s.steps(5)]) == 5 and s._astate["idx"] == 5
+        _fit(s, crit, N)
+        two = _collect(s, crit, tmp_path / "twice")
+    _same(two, fresh, exact_rel=not window)
+    assert two["end"]["keeps_x"]
+
+
+def test_criterion_of_a_lagged_fit_reused_at_another_stop_rate(monkeypatch, tmp_path):
+    """What the lagged engine configured on a criterion for its run (the flag-buffer count, its choice of the fold)
+    ends with the run: reused in a stop_rate 3 fit, the criterion gives a fresh criterion's result."""
+    new_crit = lambda: pxst.MaxIter(500) | pxst.RelError(eps=3e-3)  # noqa: E731
+    _engine(True, monkeypatch, inkernel=True, window=False)
+    res = {}
+    with pxrt.Precision(pxrt.Width.SINGLE):
+        f, g, N = _problem()
+        used = new_crit()
+        _fit(pxs.PGD(f=f, g=g, show_progress=False, stop_rate=1, folder=tmp_path / "lag"), used, N)
+        leaf = _rel_leaf(used)
+        assert leaf._lag is None and leaf._window_stats is False  # (results alone would not show a leftover)
+        for tag, crit in (("reused", used), ("fresh", new_crit())):
+            s = pxs.PGD(f=f, g=g, show_progress=False, stop_rate=3, folder=tmp_path / tag)
+            _fit(s, crit, N)
+            res[tag] = _collect(s, crit, tmp_path / tag)
+    assert 20 < res["fresh"]["idx"] < 1500
+    _same(res["reused"], res["fresh"], exact_rel=True)
