@@ -7,7 +7,6 @@ Step-size rules, momentum and initialisation follow the reference line by line (
 444-517, 763-864, 1604-1687); the iterates live on the MI355X and every update is a HIP kernel.
 """
 import math
-import sys
 import types
 import warnings
 
@@ -16,6 +15,7 @@ import numpy as np
 import pyxu_amd.abc as pxa
 import pyxu_amd.runtime as pxrt
 from pyxu_amd import _dev
+from pyxu_amd.opt.solver._recycle import Recycler
 
 __all__ = [
     *("CondatVu", "CV"),
@@ -74,9 +74,9 @@ class _PrimalDualSplitting(pxa.Solver):
         gamma = self._set_gamma(tuning_strategy)
         mst["tau"], mst["sigma"], delta = self._set_step_sizes(tau, sigma, gamma)
         mst["rho"] = self._set_momentum_term(rho, delta)
-        self._spare = None
+        # what a fit keeps outside the math state starts here (a fit that raised or was abandoned leaves nothing)
+        self._xbufs, self._zbufs = Recycler(), Recycler()  # retired x- and z-shaped iterates: the next output buffers
         self._la = None  # look-ahead step: (state arrays it was computed for, x of the next iteration)
-        self._zspare = None
         self._plan = self._fused_plan(mst["x"]) if fused else None
         if self._plan is not None:
             # the fused steps never write a tensor they have published as x while anything else references it (new
@@ -201,18 +201,6 @@ class _PrimalDualSplitting(pxa.Solver):
         state.  Call after writing the solver state (``_mstate`` x / u / z) in place outside torch."""
         self._la = None
 
-    def _take_zspare(self, z):
-        zs = self._zspare
-        self._zspare = None
-        return zs if zs is not None and zs is not z else _dev.empty_like(z)
-
-    @staticmethod
-    def _owned(t, extra=0):
-        """True iff `t` is referenced only by the solver state (+ `extra` caller locals): it may be
-        overwritten in place.  The reference allocates fresh arrays each step, so arrays a user holds
-        (z0, logged iterates, and views of user arrays such as ``batch[i]``) are never modified."""
-        return sys.getrefcount(t) <= 3 + extra and _dev.storage_exclusive(t)
-
     def m_step(self):
         raise NotImplementedError
 
@@ -293,27 +281,22 @@ class CondatVu(_PrimalDualSplitting):
             if p["la"]:
                 primed = self._primed(x, z)
                 self._la = None
-                out = self._spare
-                if out is None or out is x:
-                    out = _dev.empty_like(x)
-                z_out = self._take_zspare(z)
+                out, z_out = self._xbufs.take(x, x), self._zbufs.take(z, z)
                 _dev.pds_step_la(1, p["pre"], primed, x, None, z, p["hty"], out, None, z_out, p["q"], p["kt"], p["w"],
                                  nseg=p["nseg"])
                 mst["x"], mst["z"] = out, z_out
                 self._la = (self._la_key(out, z_out), None)
-                self._spare = x if (sys.getrefcount(x) == 2 and _dev.storage_exclusive(x)) else None
-                self._zspare = z if (sys.getrefcount(z) == 2 and _dev.storage_exclusive(z)) else None
+                # the previous iterate's arrays (one local each) are reused when nothing else holds them
+                self._xbufs.retire(x, 1)
+                self._zbufs.retire(z, 1)
                 return
-            out = self._spare
-            if out is None or out is x:
-                out = _dev.empty_like(x)
-            z_out = z if self._owned(z, extra=1) else _dev.empty_like(z)
+            out, z_out = self._xbufs.take(x, x), _dev.empty_like(z)
             if "slab" in p:
                 self._slab_step(x, None, z, out, None, z_out)
             else:
                 _dev.pds_step(1, p["pre"], x, None, z, p["hty"], out, None, z_out, p["q"], p["w"], nseg=p["nseg"])
             mst["x"], mst["z"] = out, z_out
-            self._spare = x if (sys.getrefcount(x) == 2 and _dev.storage_exclusive(x)) else None
+            self._xbufs.retire(x, 1)
             return
         x = mst["x"]
         tau = mst["tau"]
@@ -406,24 +389,19 @@ class PD3O(_PrimalDualSplitting):
                 x_cur = self._la[1] if primed else None
                 self._la = None  # drop its references before the ownership checks
                 if x_cur is None:
-                    x_cur = x if self._owned(x, extra=1) else _dev.empty_like(x)
-                x_next = self._spare
-                if x_next is None or x_next is x_cur:
-                    x_next = _dev.empty_like(x)
-                u_out = u if self._owned(u, extra=1) else _dev.empty_like(u)
-                z_out = self._take_zspare(z)
+                    x_cur = _dev.empty_like(x)
+                x_next, u_out, z_out = self._xbufs.take(x, x_cur), _dev.empty_like(u), self._zbufs.take(z, z)
                 _dev.pds_step_la(0, p["pre"], primed, x_cur, u, z, p["hty"], x_next, u_out, z_out, p["q"], None,
                                  p["w"], nseg=p["nseg"])
                 mst["x"], mst["u"], mst["z"] = x_cur, u_out, z_out
                 self._la = (self._la_key(x_cur, u_out, z_out), x_next)
                 del x_next, u_out
-                # the previous iterate's arrays are reused when nothing else holds them
-                self._spare = x if (x is not x_cur and sys.getrefcount(x) == 2 and _dev.storage_exclusive(x)) else None
-                self._zspare = z if (sys.getrefcount(z) == 2 and _dev.storage_exclusive(z)) else None
+                # the previous iterate's arrays (one local each) are reused when nothing else holds them
+                if x is not x_cur:
+                    self._xbufs.retire(x, 1)
+                self._zbufs.retire(z, 1)
                 return
-            x_out = x if self._owned(x, extra=1) else _dev.empty_like(x)
-            u_out = u if self._owned(u, extra=1) else _dev.empty_like(u)
-            z_out = z if self._owned(z, extra=1) else _dev.empty_like(z)
+            x_out, u_out, z_out = _dev.empty_like(x), _dev.empty_like(u), _dev.empty_like(z)
             if "slab" in p:
                 self._slab_step(None, u, z, x_out, u_out, z_out)
             else:

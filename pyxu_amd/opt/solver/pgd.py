@@ -2,7 +2,6 @@
 import collections
 import itertools
 import os
-import sys
 import math
 import warnings
 
@@ -11,6 +10,7 @@ import pyxu_amd.runtime as pxrt
 from pyxu_amd import _dev
 from pyxu_amd.abc._stoplink import StepStats
 from pyxu_amd.opt.solver._fused import match_pgd_deblur
+from pyxu_amd.opt.solver._recycle import Recycler
 from pyxu_amd.util import copy_if_unsafe
 
 __all__ = ["PGD"]
@@ -85,8 +85,7 @@ class PGD(pxa.Solver):
 
         mst = self._mstate
         # everything a fit keeps outside the math state starts here (a run that raised or was abandoned leaves nothing)
-        self._spare = None  # a retired iterate that nothing else references: the next output buffer
-        self._pool = []  # retired iterates that something still references (the lagged engine's held states)
+        self._bufs = Recycler(self._astate)  # retired iterates: the fused step's output buffers
         self._spec_refs = 0  # references the engine's rollback token holds to x_prev
         self._x_check = None  # the x of the last stop check (RelError partials against it)
         self._wpar_i = 0  # which of the two window-partials buffers the last launch wrote
@@ -158,7 +157,7 @@ class PGD(pxa.Solver):
         mst["x"], mst["x_prev"] = token
         mst["a"].rewind(1)
         mst.link.drop_offers()
-        self._spare = None
+        self._bufs.clear()
         self._spec_refs = 0
 
     # lagged stop checks (abc/solver.py _lag_loop): a check's state is (x, x_prev); dropping the steps launched after
@@ -187,52 +186,14 @@ class PGD(pxa.Solver):
         mst["a"].rewind(undone)
         mst.link.drop_offers()
         self._wpub_pending = None
-        self._spare = None
         self._x_check = None
-        self._pool = []
+        self._bufs.clear()
 
-    # Output buffers.  The old x_prev becomes the next output buffer iff nobody else holds it (the reference allocates
-    # fresh arrays, so user-held results must never be overwritten): its Python reference count and its storage's use
-    # count say so.  Under the lagged engine the held check states keep it referenced, and every step would allocate
-    # (torch.empty_like: several us of host time per step at stop_rate 1, where the host sets the pace): there, the
-    # iterates the window steps retire wait in a small pool and are reused once nothing references them (the same
-    # test: a held state, a steps() item or a user view keeps a buffer out of reuse).
-    _POOL_MAX = 16
-
-    def _take(self, x, xp):
-        """An output buffer for the step from (x, xp)."""
-        out = self._spare
-        if out is not None and out is not x and out is not xp:
-            return out
-        pool = self._pool
-        for i in range(len(pool)):
-            b = pool[i]
-            # references: the pool's, b, getrefcount's argument
-            if (sys.getrefcount(b) == 3 and b is not x and b is not xp and b.shape == x.shape and b.dtype == x.dtype
-                    and _dev.storage_exclusive(b)):
-                del pool[i]
-                return b
-        return _dev.empty_like(x)
-
-    def _retire(self, xp, x, held, pool=False):
-        """xp has just left the state (x is the new x_prev): the next output buffer iff nobody else holds it.  `held`
-        is sys.getrefcount(xp) as the step took it with xp in one local of its own (2: that local and getrefcount's
-        argument, plus what the engine's rollback token holds).  With `pool`, a buffer still held waits in the pool."""
-        free = held == 2 + self._spec_refs
-        self._spec_refs = 0
-        if free and xp.data_ptr() != x.data_ptr() and _dev.storage_exclusive(xp):
-            self._spare = xp
-            return
-        self._spare = None
-        if not pool:
-            return
-        pool = self._pool
-        if self._astate.get("lag") is None:  # (a pool only while the lagged engine runs; emptied when it ends)
-            pool.clear()
-            return
-        pool.append(xp)
-        if len(pool) > self._POOL_MAX:
-            del pool[0]
+    # Output buffers (_recycle.py).  The old x_prev becomes the next output buffer iff nobody else holds it.  Under the
+    # lagged engine the held check states keep it referenced, and every step would allocate (torch.empty_like: several
+    # us of host time per step at stop_rate 1, where the host sets the pace): there, the iterates the window steps
+    # retire wait in the recycler's pool and are reused once nothing references them.  A step holds the x_prev that
+    # leaves the state in one local; the engine's rollback token holds `_spec_refs` more references to it.
 
     def m_step(self):
         mst = self._mstate
@@ -259,7 +220,7 @@ class PGD(pxa.Solver):
         fold launch (PXA_LAG_PUB=0: a fold launch behind the step instead)."""
         mst, p = self._mstate, self._plan
         x, xp = mst["x"], mst["x_prev"]
-        out = self._take(x, xp)
+        out = self._bufs.take(x, x, xp)
         tau = mst["tau"]
         if self._LAG_PUB:
             wp = p.get("wparts")
@@ -272,8 +233,9 @@ class PGD(pxa.Solver):
         else:
             p["plan"].step_window(x, xp, p["hty"], out, a, tau, tau * p["prox_scale"], p["parts"], wnd.buffer, wnd.seq)
         mst["x_prev"], mst["x"] = x, out
-        held = sys.getrefcount(xp)
-        self._retire(xp, x, held, pool=True)
+        known = 1 + self._spec_refs
+        self._spec_refs = 0
+        self._bufs.retire(xp, known, x, True)  # (pooled while still held)
 
     def _step_epilogue(self, a, link):
         """The launch right before a stop check also computes that check's RelError partials in its epilogue (the
@@ -282,7 +244,7 @@ class PGD(pxa.Solver):
         at stop_rate 1, else the x this solver saw at that check (self._x_check, the same tensor object)."""
         mst, p, ast = self._mstate, self._plan, self._astate
         x, xp = mst["x"], mst["x_prev"]
-        out = self._take(x, xp)
+        out = self._bufs.take(x, x, xp)
         tau = mst["tau"]
         sr = ast.get("stop_rate")
         if sr is not None and (ast["idx"] - 1) % sr == 0:
@@ -309,8 +271,9 @@ class PGD(pxa.Solver):
             link.step_stats = StepStats("x", out, xref, parts, p["rows"], p["tiles_per_row"],
                                         (buf, seq) if buf is not None else None)
         mst["x_prev"], mst["x"] = x, out
-        held = sys.getrefcount(xp)
-        self._retire(xp, x, held)
+        known = 1 + self._spec_refs
+        self._spec_refs = 0
+        self._bufs.retire(xp, known, x)
 
     def default_stop_crit(self):
         from pyxu_amd.opt.stop import RelError
