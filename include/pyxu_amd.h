@@ -294,6 +294,30 @@ int pxa_nlcg_direction(int dtype, int variant, int restart, int64_t rows, int64_
                        const void* p, void* p_new, const double* gg0, double* gg_out, double* gg_host, uint32_t* flags,
                        uint32_t seq, void* work, void* stream);
 
+/* Re-orthogonalisation of a Krylov vector against a basis (math/_lanczos.py, LinOp.svdvals): V is a row-major
+ * array of j <= 64 rows of n entries with row stride ldv >= n (elements), w one row of n, c / c_out / c_next j
+ * device doubles.  Two classical Gram-Schmidt passes are pxa_krylov_dots, pxa_krylov_update with c_next,
+ * pxa_krylov_update with nrm2_out: three launches, V streamed twice (the second look of the first update re-reads
+ * the workgroup's chunk from cache).
+ *   pxa_krylov_dots    c_out[i] = scale * <V_i, w>, i < j; scale a device double or NULL (1).
+ *   pxa_krylov_update  w_out = w - sum_i c[i] V_i (w_out == w allowed, otherwise disjoint from w and V), then
+ *                      c_next[i] = <V_i, w_out> and *nrm2_out = ||w_out||^2 of the stored (rounded) w_out; either
+ *                      may be NULL, c_next == NULL skips the second look at V.  c_next != c.
+ *   pxa_krylov_normalize  out = x / sqrt(*nrm2) (out == x allowed); *nrm2 == 0 gives a zero row, never inf / NaN.
+ * All products and sums in double; the update accumulates in double with double coefficients and rounds once.
+ * Fixed partition (column chunks of pxa_krylov_chunk(dtype) elements, at most 2048 workgroups striding over them)
+ * and fixed fold order, no floating-point atomics: the same call gives the same bits.  16-byte accesses when V, w,
+ * w_out are 16-byte aligned and ldv is a whole number of 16-byte vectors, scalar accesses otherwise (other sum
+ * order).  `work`: pxa_krylov_workspace_bytes(j, n) bytes, 16-byte aligned; calls sharing it must be ordered (one
+ * stream).  j > 64: PXA_ERR_UNSUPPORTED, nothing launched.  No allocation, no synchronisation. */
+int64_t pxa_krylov_chunk(int dtype);
+size_t pxa_krylov_workspace_bytes(int64_t j, int64_t n);
+int pxa_krylov_dots(int dtype, int64_t j, int64_t n, const void* V, int64_t ldv, const void* w, const double* scale,
+                    double* c_out, void* work, void* stream);
+int pxa_krylov_update(int dtype, int64_t j, int64_t n, const void* V, int64_t ldv, const void* w, const double* c,
+                      void* w_out, double* c_next, double* nrm2_out, void* work, void* stream);
+int pxa_krylov_normalize(int dtype, int64_t n, const void* x, const double* nrm2, void* out, void* stream);
+
 /* Armijo test of one backtracking trial for every row (math/linesearch.py:71-93), one launch of one workgroup,
  * one wavefront per row in turn: d_f = (T)c (T)<g, p>, rhs = f_x + a d_f (product, then sum, each rounded to T, never
  * contracted), fail = f_trial > rhs (a NaN on either side is no failure, as `lhs > rhs` in the reference); on fail

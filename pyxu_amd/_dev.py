@@ -613,6 +613,50 @@ def cg_update_xr(x, r, p, ap, rr, work):
                                stream()), "pxa_cg_update_xr")
 
 
+def krylov_chunk(like):
+    """Columns per workgroup chunk of the pxa_krylov_* kernels for `like`'s dtype."""
+    return int(lib.pxa_krylov_chunk(dtcode(like)))
+
+
+def krylov_workspace(j, n, like):
+    """Workspace of pxa_krylov_dots / pxa_krylov_update for up to j rows of n (float64 device tensor)."""
+    wsz = int(lib.pxa_krylov_workspace_bytes(int(j), int(n)))
+    return _torch().zeros((max(wsz // 8, 2),), dtype=_torch().float64, device=like.device)
+
+
+def _krylov_rows(V, j, w):
+    """(ldv, n) of the first j rows of V, a (rows, n) tensor or view with unit column stride, against w (n,)."""
+    n = w.numel()
+    assert V.ndim == 2 and V.shape[0] >= j and V.shape[1] == n and V.stride(1) == 1 and V.dtype == w.dtype
+    assert w.is_cuda and V.is_cuda and (w.ndim == 1 and (n == 1 or w.stride(0) == 1))
+    return (V.stride(0) if V.shape[0] > 1 else n), n
+
+
+def krylov_dots(V, j, w, c_out, work, scale=None):
+    """pxa_krylov_dots: c_out[i] = scale * <V[i], w>, i < j (float64 device vector); scale: float64 device scalar."""
+    ldv, n = _krylov_rows(V, j, w)
+    check(lib.pxa_krylov_dots(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), ptr(scale) if scale is not None else None,
+                              ptr(c_out), ptr(work), stream()), "pxa_krylov_dots")
+    return c_out
+
+
+def krylov_update(V, j, w, c, w_out, work, c_next=None, nrm2_out=None):
+    """pxa_krylov_update: w_out = w - sum_i c[i] V[i] (w_out may be w), c_next[i] = <V[i], w_out> and nrm2_out =
+    ||w_out||^2 when given (float64 device)."""
+    ldv, n = _krylov_rows(V, j, w)
+    assert w_out.dtype == w.dtype and w_out.numel() == n
+    check(lib.pxa_krylov_update(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), ptr(c), ptr(w_out),
+                                ptr(c_next) if c_next is not None else None,
+                                ptr(nrm2_out) if nrm2_out is not None else None, ptr(work), stream()), "pxa_krylov_update")
+    return w_out
+
+
+def krylov_normalize(x, nrm2, out):
+    """pxa_krylov_normalize: out = x / sqrt(nrm2) with nrm2 a float64 device scalar (a zero row for nrm2 == 0)."""
+    check(lib.pxa_krylov_normalize(dtcode(x), x.numel(), ptr(x), ptr(nrm2), ptr(out), stream()), "pxa_krylov_normalize")
+    return out
+
+
 NLCG_FR, NLCG_PR = 0, 1  # pxa_nlcg_direction variants
 _CG_BLOCKS = 64  # partials per row of the CG / NLCG tail partition (csrc/common.hpp kCgBlocks)
 

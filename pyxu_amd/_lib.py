@@ -64,6 +64,11 @@ EXPORTS = {
     "pxa_nlcg_workspace_bytes": (sz, [i64]),
     "pxa_nlcg_direction": (i32, [i32, i32, i32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, ct.c_uint32, vp, vp]),
     "pxa_ls_armijo": (i32, [i32, i64, vp, vp, vp, ct.c_int32, f64, f64, vp, vp, vp, vp, ct.c_uint32, vp]),
+    "pxa_krylov_chunk": (i64, [i32]),
+    "pxa_krylov_workspace_bytes": (sz, [i64, i64]),
+    "pxa_krylov_dots": (i32, [i32, i64, i64, vp, i64, vp, vp, vp, vp, vp]),
+    "pxa_krylov_update": (i32, [i32, i64, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]),
+    "pxa_krylov_normalize": (i32, [i32, i64, vp, vp, vp, vp]),
     "pxa_proxadam_blocks": (i32, [i64, i64]),
     "pxa_proxadam_workspace_bytes": (sz, [i64, i64]),
     "pxa_proxadam_moments": (i32, [i32, i32, i32, i64, i64, f64, f64, f64, f64, f64, f64, f64, f64, f64, f64, vp, vp, vp,

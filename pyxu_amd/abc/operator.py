@@ -598,10 +598,40 @@ class LinOp(DiffMap):
                 L_prev = L
         return float(L)
 
-    def svdvals(self, k=1, which="LM", **kwargs):
-        if k != 1 or which.upper() != "LM":
-            raise NotImplementedError("pyxu_amd: only the largest singular value (k=1, 'LM') is available on device.")
-        return np.array([self._power_lipschitz(**kwargs)], dtype=pxrt.getPrecision().value)
+    def svdvals(self, k=1, which="LM", gpu=False, **kwargs):
+        """The k largest (which="LM") or smallest ("SM") singular values, ascending, as a (k,) array of the runtime
+        precision (operator.py:1500-1567).  ``gpu`` is accepted for signature parity and ignored.
+
+        * k == 1, "LM", no ``solver`` keyword: the device power iteration on A^T A (``n_iter``, ``tol``, ``seed``).
+        * k >= min(shape) // 2: the matrix is built with asarray() (DenseWarning) and numpy.linalg.svd runs on the
+          host in float64, as the reference reverts to a dense SVD.
+        * otherwise, and with ``solver="lanczos"``: the thick-restart Lanczos of pyxu_amd.math._lanczos on the smaller
+          Gram operator (``ncv``, ``tol``, ``maxiter``, ``v0``, ``seed``; other keywords are ignored).  "SM" needs
+          iterations on the order of the condition number and raises RuntimeError at ``maxiter`` restart cycles.
+        """
+        which = str(which).upper().strip()
+        if which not in ("LM", "SM"):
+            raise ValueError(f"which: expected 'LM' or 'SM', got {which!r}.")
+        k, n = int(k), min(self.shape)
+        solver = kwargs.get("solver")
+        if k == 1 and which == "LM" and solver is None:
+            return np.array([self._power_lipschitz(**kwargs)], dtype=pxrt.getPrecision().value)
+        if not 1 <= k <= n:
+            raise ValueError(f"k: expected 1 <= k <= min(shape) = {n}, got {k}.")
+        if solver is not None and str(solver).lower().strip() != "lanczos":
+            raise ValueError(f"solver: expected 'lanczos', got {solver!r}.")
+        if k >= n // 2 and solver is None:
+            import warnings
+
+            from pyxu_amd.info.warning import DenseWarning
+
+            warnings.warn(f"svdvals(k={k}) of a {self.shape} operator: computing a dense representation.", DenseWarning)
+            s = np.sort(np.linalg.svd(np.asarray(self.asarray(xp=np), dtype=np.float64), compute_uv=False))
+            return (s[-k:] if which == "LM" else s[:k]).astype(pxrt.getPrecision().value)
+        from pyxu_amd.math._lanczos import lanczos_svdvals
+
+        kw = {key: kwargs[key] for key in ("ncv", "tol", "maxiter", "v0", "seed", "_stats") if key in kwargs}
+        return lanczos_svdvals(self, k, which, **kw)
 
     def asarray(self, xp=None, dtype=None):
         """Matrix representation (device tensor unless xp is numpy), built column-block-wise."""

@@ -64,7 +64,9 @@ def block_diag(ops, **kwargs):
         k = kw.get("k", 1)
         if kw.get("which", "LM").upper() == "SM":
             return _.__class__.svdvals(_, **kw)
-        parts = np.concatenate([np.atleast_1d(np.asarray(o.svdvals(**kw))) for o in _._block.values()])
+        # a block smaller than k contributes all its values (its own svdvals rejects k > min(shape))
+        parts = np.concatenate([np.atleast_1d(np.asarray(o.svdvals(**{**kw, "k": min(k, *o.shape)})))
+                                for o in _._block.values()])
         return np.sort(parts, axis=None)[-k:]
 
     @pxrt.enforce_precision(i=("arr", "damp"))
