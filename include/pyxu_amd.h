@@ -48,6 +48,24 @@ extern "C" {
 
 #define PXA_MAX_DIM 4    /* spatial rank supported by stencil / gradient kernels */
 #define PXA_MAX_TAPS 64  /* taps per separable-axis pass (kernel-argument resident) */
+#define PXA_CG_BLOCKS 64 /* partials per row of the CG / NLCG tail partition (workspace planes of rows * 64 doubles) */
+#define PXA_PDS_TAP_SLOTS 17 /* per-axis tap slots of pxa_pds_step's offs / coefs (reach <= 8: 2 * 8 + 1) */
+
+/* pxa_nlcg_direction variants. */
+#define PXA_NLCG_FR 0 /* Fletcher-Reeves */
+#define PXA_NLCG_PR 1 /* Polak-Ribiere+ */
+
+/* pxa_proxadam_moments variants, and the planes of rows * nb doubles that open a ProxAdam workspace. */
+#define PXA_PROXADAM_ADAM 0
+#define PXA_PROXADAM_AMSGRAD 1
+#define PXA_PROXADAM_PADAM 2
+#define PXA_PROXADAM_PLANES 5
+
+/* Element-wise prox kinds of pxa_proxadam_sub_step and pxa_langevin_step (which also takes 0: no g). */
+#define PXA_PROX_L1 1
+#define PXA_PROX_POS 2
+#define PXA_PROX_POSL1 3
+#define PXA_PROX_BOX 4
 
 /* Boundary modes of Pad (operator/linop/pad.py:145-160). */
 #define PXA_MODE_CONSTANT 0
@@ -259,18 +277,21 @@ int pxa_row_shrink(int dtype, int mode, int64_t rows, int64_t n, const void* x, 
  * != rr) and rr_host (pinned / device-mapped host memory, may be NULL) receive rr'; with `flags` (rows words
  * of pxa_host_alloc memory, rr_host then in that memory too) flag[row] is set to `seq` once rr_host[row] is
  * visible to the host, so the stop check polls it instead of waiting for a stream event.  All sums in double
- * with a fixed partition and order.  `work`: pxa_cg_update_workspace_bytes(rows) bytes. */
+ * with a fixed partition and order.  `work`: pxa_cg_update_workspace_bytes(rows) bytes
+ *   = 2 * rows * PXA_CG_BLOCKS doubles: plane 0, work[0 .. rows * PXA_CG_BLOCKS), the <p, A p> partials; plane 1,
+ *   work + rows * PXA_CG_BLOCKS doubles, the ||r'||^2 partials; row r's partials at [r * nb, (r + 1) * nb) of its
+ *   plane, nb = min(PXA_CG_BLOCKS, ceil(n / 256)). */
 size_t pxa_cg_update_workspace_bytes(int64_t rows);
 int pxa_cg_update(int dtype, int64_t rows, int64_t n, void* x, void* r, void* p, const void* ap, const double* rr,
                   double* rr_out, double* rr_host, uint32_t* flags, uint32_t seq, void* work, void* stream);
 
-/* pxa_cg_update without its first launch: work[0 .. rows * 64) already holds the <p, A p> partials, written
+/* pxa_cg_update without its first launch: work[0 .. rows * PXA_CG_BLOCKS) already holds the <p, A p> partials, written
  * together with A p by pxa_dense_normal_pdot (same partition and bits as pxa_cg_update's own). */
 int pxa_cg_update_tail(int dtype, int64_t rows, int64_t n, void* x, void* r, void* p, const void* ap, const double* rr,
                        double* rr_out, double* rr_host, uint32_t* flags, uint32_t seq, void* work, void* stream);
 
 /* The CG tail's first half alone (pxa_cg_update_tail without the p update): x += alpha p, r -= alpha A p, and the
- * ||r'||^2 partials at work + rows * 64 doubles, for a following pxa_dense_normal_pdot_pfold that forms p' = r' +
+ * ||r'||^2 partials at work + rows * PXA_CG_BLOCKS doubles, for a following pxa_dense_normal_pdot_pfold that forms p' = r' +
  * beta p inside its operator pass (cg.py:125-153; same bits as pxa_cg_update_tail + pxa_dense_normal_pdot). */
 int pxa_cg_update_xr(int dtype, int64_t rows, int64_t n, void* x, void* r, const void* p, const void* ap, const double* rr,
                      void* work, void* stream);
@@ -285,9 +306,10 @@ int pxa_cg_update_xr(int dtype, int64_t rows, int64_t n, void* x, void* r, const
  * which the next line search needs (math/linesearch.py:72).  gg0: sum g0^2 per row as published by the previous
  * call (device double); a plain IEEE division, so gg0 == 0 gives inf / NaN as in the reference.  gg_out (device,
  * != gg0) and gg_host / flags / seq receive sum g1^2 exactly as rr_out / rr_host / flags / seq of pxa_cg_update.
- * `work`: pxa_nlcg_workspace_bytes(rows) bytes = three planes of rows * 64 doubles; on return the third plane
- * (work + rows * 128 doubles) holds the <g1, p_new> partials, row r's at [r * nb, (r + 1) * nb) with
- * nb = min(64, ceil(n / 256)), for pxa_ls_armijo.  Partition and fold order of pxa_cg_update, no atomics:
+ * `work`: pxa_nlcg_workspace_bytes(rows) bytes = 3 * rows * PXA_CG_BLOCKS doubles, three planes of
+ * rows * PXA_CG_BLOCKS each (sum g1^2, sum g1 (g1 - g0), <g1, p_new>); on return the third plane
+ * (work + 2 * rows * PXA_CG_BLOCKS doubles) holds the <g1, p_new> partials, row r's at [r * nb, (r + 1) * nb) with
+ * nb = min(PXA_CG_BLOCKS, ceil(n / 256)), for pxa_ls_armijo.  Partition and fold order of pxa_cg_update, no atomics:
  * the same bits run to run.  rows <= 65535. */
 size_t pxa_nlcg_workspace_bytes(int64_t rows);
 int pxa_nlcg_direction(int dtype, int variant, int restart, int64_t rows, int64_t n, const void* g1, const void* g0,
@@ -332,8 +354,13 @@ int pxa_ls_armijo(int dtype, int64_t rows, const void* f_trial, const void* f_x,
  * over nb = pxa_proxadam_blocks(rows, n) workgroups (blocks_per_row: up to 1024), workgroup b owning elements
  * [b chunk, (b + 1) chunk), chunk = ceil(n / nb) rounded up to a whole 16-byte vector.  16-byte accesses when every
  * operand is 16-byte aligned and (rows == 1 or n is a whole number of vectors), scalar accesses otherwise.
- * `work`: pxa_proxadam_workspace_bytes(rows, n) bytes: five planes of rows * nb doubles (the psi maxima; two pairs
- * of RelError partials, used alternately), rows doubles (psimax), rows int32 state words, two int32 counters.
+ * `work`: pxa_proxadam_workspace_bytes(rows, n) bytes, with P = rows * nb, in doubles:
+ *   [0, P)                 the psi maxima per workgroup
+ *   [P, 3 P), [3 P, 5 P)   two pairs of RelError partial planes (sum (z_new - z)^2, then sum z^2); sub-step launch k
+ *                          writes the pair at P * (1 + 2 * (k & 1))
+ *   [5 P, 5 P + rows)      psimax per row (5 = PXA_PROXADAM_PLANES)
+ * then rows int32 state words and two int32 counters (padded to a whole double):
+ *   bytes = (PXA_PROXADAM_PLANES * P + rows) * 8 + (rows + 2 + (rows & 1)) * 4.
  *
  * pxa_proxadam_moments: one launch for everything between g = grad f(x) and x' (prox_adam.py:341-370); the scalars
  * are cast to the working type T, omb1 / omb2 are 1 - b1 / 1 - b2 and c1 = 1 - b1^t, c2 = sqrt(1 - b2^t) the bias
@@ -840,7 +867,7 @@ int pxa_pds_kernel_ms(double* ms_abc, int reset);
  * weight prox_w).  Three launches: axis-0 march, in-plane tile, dual update (pds3d.hip).
  *   geom  = {stack, y_images, n0, n1, n2, D}: `stack` volumes of (n0, n1, n2) (n0 = 1, D = 2 for
  *           images); z is (stack, D, n0, n1, n2) direction-major, direction d on axis d + 3 - D.
- *   ntaps[3], offs[3][17], coefs[3][17]: the separable taps of S per axis (code-generation order;
+ *   ntaps[3], offs[3][PXA_PDS_TAP_SLOTS], coefs[3][PXA_PDS_TAP_SLOTS]: the separable taps of S per axis (code-generation order;
  *           axis 0 = {[0], [1.0]} when it is not blurred).
  *   diff  = {c0[3], c1[3]}: forward-difference taps per AXIS, (K x)[i] = c0 x[i] + c1 x[i + e_a]
  *           (-1/h, 1/h); entries of non-differentiated axes are ignored.

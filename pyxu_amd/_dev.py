@@ -49,23 +49,147 @@ def dtcode(t) -> int:
     raise TypeError(f"pyxu_amd: unsupported dtype {t.dtype} (float32/float64 only).")
 
 
-def require(t, name="arr"):
-    """Validate a device operand: CUDA (ROCm) tensor, float32/64, contiguous."""
-    if _TIMER is not None:  # other device work is about to be enqueued: close the timing window
-        _TIMER.interrupt()
+class _DtypeMismatch(TypeError, ValueError):
+    """An operand whose dtype differs from that of the call's other operands.  A TypeError like every dtype error of
+    this module; also a ValueError, which the NUFFT, ProxAdam and sampler entries have always raised for it."""
+
+
+_FLOATS = ()  # (torch.float32, torch.float64) once torch is in
+
+
+def _floats():
+    global _FLOATS
+    _FLOATS = (_torch().float32, _torch().float64)
+    return _FLOATS
+
+
+def _operand(t, name, dtype, like, numel, shape, ctx, pinned=False):
+    """The checks `require` (inputs) and `written` (outputs) share: a device tensor (with `pinned`, pinned host
+    memory too) of float32 / float64 or of the torch dtype named `dtype`, optionally of like's dtype, of `numel`
+    elements, of `shape`.  TypeError for kind, device and dtype, ValueError for size."""
     if not (type(t).__module__.startswith("torch") and hasattr(t, "is_cuda")):
         raise TypeError(
             f"pyxu_amd: `{name}` must be an MI355X device tensor (got {type(t).__name__}); "
             "move host data with pyxu_amd.util.to_device()."
         )
-    if not t.is_cuda:
+    if not (t.is_cuda or (pinned and t.is_pinned())):
         raise TypeError(f"pyxu_amd: `{name}` lives on {t.device}; pyxu_amd computes on the MI355X only.")
-    dtcode(t)
+    if dtype is None:
+        dtcode(t)
+    elif t.dtype != getattr(_torch(), dtype):
+        raise TypeError(f"pyxu_amd: `{name}` has dtype {t.dtype}, {ctx} needs {dtype}.")
+    if like is not None and t.dtype != like.dtype:
+        raise _DtypeMismatch(f"pyxu_amd: `{name}` has dtype {t.dtype}, {ctx} has {like.dtype}.")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"pyxu_amd: `{name}` holds {t.numel()} elements, {ctx} needs {numel}.")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"pyxu_amd: `{name}` has shape {tuple(t.shape)}, {ctx} needs {tuple(shape)}.")
+
+
+def require(t, name="arr", dtype=None, like=None, numel=None, shape=None, ctx="the call"):
+    """An input operand: a device tensor, float32 / float64 or the torch dtype named `dtype` ("float64", "int32",
+    "int64", "bool"), optionally of like's dtype, `numel` elements, `shape`.  A non-contiguous input is copied."""
+    if _TIMER is not None:  # other device work is about to be enqueued: close the timing window
+        _TIMER.interrupt()
+    # (a call that passes skips the nested call: host cost per call in profiles/dev_binding_host_ab.txt)
+    if not (dtype is None and shape is None and getattr(t, "is_cuda", False)
+            and (t.dtype in (_FLOATS or _floats()) if like is None else t.dtype == like.dtype)
+            and (numel is None or t.numel() == numel)):
+        _operand(t, name, dtype, like, numel, shape, ctx)
     return t if t.is_contiguous() else t.contiguous()
+
+
+def require_bool(c):
+    return require(c, "condition", dtype="bool")
+
+
+def written(t, name="out", dtype=None, like=None, numel=None, at_least=None, apart=(), ctx="the call", pinned=False):
+    """An operand a kernel writes (`out=`, an in-place operand, a workspace): as `require`, but taken as it is, so a
+    non-contiguous one is a ValueError, never a copy.  Sizes go by `numel` (callers pass flat and shaped views of one
+    buffer) or `at_least` elements; a contiguous view may start off a 16-byte boundary (the kernels then take their
+    scalar path).  It must not start where any tensor of `apart` starts (None entries are skipped)."""
+    if (dtype is None and at_least is None and not apart and getattr(t, "is_cuda", False) and t.is_contiguous()
+            and (t.dtype in (_FLOATS or _floats()) if like is None else t.dtype == like.dtype)
+            and (numel is None or t.numel() == numel)):
+        return t  # (the common `out=` that passes, in one expression; everything else is named below)
+    _operand(t, name, dtype, like, numel, None, ctx, pinned)
+    if not t.is_contiguous():
+        raise ValueError(f"pyxu_amd: `{name}` is written in place and must be contiguous.")
+    if at_least is not None and t.numel() < at_least:
+        raise ValueError(f"pyxu_amd: `{name}` holds {t.numel()} elements, {ctx} needs at least {at_least}.")
+    for o in apart:
+        if o is not None and o.data_ptr() == t.data_ptr():
+            raise ValueError(f"pyxu_amd: `{name}` aliases another operand of {ctx}.")
+    return t
+
+
+def _out(out, like, shape=None, apart=()):
+    """The result of a wrapper: a fresh contiguous tensor of `shape` (like's own when None) in like's dtype, or the
+    caller's `out`, checked as `written` with that many elements."""
+    if out is None:
+        return empty_like(like) if shape is None else empty(shape, like)
+    numel = like.numel() if shape is None else int(np.prod(shape))
+    return written(out, "out", like=like, numel=numel, apart=apart)
+
+
+def flag_buffer(fb, name, values, flags):
+    """A HostFlagBuffer with at least `values` values and exactly `flags` flags."""
+    if not isinstance(fb, HostFlagBuffer):
+        raise TypeError(f"pyxu_amd: `{name}` must be a HostFlagBuffer (got {type(fb).__name__}).")
+    if len(fb.values) < values or len(fb.flags) != flags:
+        raise ValueError(f"pyxu_amd: `{name}` must be a HostFlagBuffer of >= {values} values and {flags} flags.")
+    return fb
+
+
+def _publication(host, name=None, rows=None):
+    """(seq, values pointer, flags pointer) of a statistic a kernel publishes to `host`: a HostFlagBuffer (a new
+    sequence number; checked to hold `rows` values and flags when `rows` is given), a pinned tensor, or None."""
+    if isinstance(host, HostFlagBuffer):
+        if rows is not None:
+            flag_buffer(host, name, rows, rows)
+        return host.next_seq(), host.vptr, host.fptr
+    return 0, (None if host is None else host.data_ptr()), None
 
 
 def ptr(t) -> int:
     return t.data_ptr()
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+def _launch(fn, *args):
+    """The C entry fn(*args) under the bench timer hook (set_launch_timer; normally absent); a non-zero status raises."""
+    timer = _TIMER
+    if timer is not None:
+        timer.begin()
+    r = fn(*args)
+    if r:
+        check(r, fn.__name__)
+    if timer is not None:
+        timer.end()
+
+
+def _workspace_bytes(name, *args, unsupported_ok=False):
+    """lib.<name>(*args), a `*_workspace_bytes` query.  Its (size_t)-1 answer, arguments outside the kernel's
+    envelope, raises as PXA_ERR_UNSUPPORTED (or returns None with `unsupported_ok`)."""
+    n = int(getattr(lib, name)(*args))
+    if n == (1 << 64) - 1:
+        if unsupported_ok:
+            return None
+        check(-3, name)  # PXA_ERR_UNSUPPORTED
+    return n
+
+
+def _workspace(name, like, *args, f64=False):
+    """The workspace that query asks for, on like's device: float64 of at least one element with `f64`, otherwise
+    uint8, or None when no byte is needed."""
+    n = _workspace_bytes(name, *args)
+    torch = _torch()
+    if f64:
+        return torch.empty((max((n + 7) // 8, 1),), dtype=torch.float64, device=like.device)
+    return torch.empty((n,), dtype=torch.uint8, device=like.device) if n else None
 
 
 def _raw_stream_fn():
@@ -270,17 +394,14 @@ def scalar_dt(x):
 
 
 # ------------------------------------------------------------------ element-wise
+# (`out` may be any input: include/pyxu_amd.h, element-wise kernels)
 def axpby(a, x, b=0.0, y=None, out=None):
     """out = a*x + b*y."""
     x = require(x, "x")
     if y is not None:
-        y = require(y, "y")
-        assert y.numel() == x.numel() and y.dtype == x.dtype
-    out = empty_like(x) if out is None else out
-    check(
-        lib.pxa_axpby(dtcode(x), x.numel(), float(a), ptr(x), float(b), ptr(y) if y is not None else None, ptr(out), stream()),
-        "pxa_axpby",
-    )
+        y = require(y, "y", like=x, numel=x.numel())
+    out = _out(out, x)
+    check(lib.pxa_axpby(dtcode(x), x.numel(), float(a), ptr(x), float(b), _p(y), ptr(out), stream()), "pxa_axpby")
     return out
 
 
@@ -289,7 +410,7 @@ def axpby_bcast(a, x, b, y, out=None):
     x, y = require(x, "x"), require(y, "y")
     if y.numel() == x.numel():
         return axpby(a, x, b, y, out=out)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_axpby_bcast(dtcode(x), x.numel(), float(a), ptr(x), float(b), ptr(y), y.numel(), ptr(out), stream()), "pxa_axpby_bcast")
     return out
 
@@ -298,7 +419,7 @@ def axpy_rows(c, s, x, y, out=None):
     """out[r] = y[r] + s * c[r] * x[r] for x, y of shape (rows, n); c a (rows,) device vector."""
     x, y, c = require(x, "x"), require(y, "y"), require(c, "c")
     rows = c.numel()
-    out = empty_like(y) if out is None else out
+    out = _out(out, y)
     check(lib.pxa_axpy_rows(dtcode(x), rows, x.numel() // max(rows, 1), ptr(c), float(s), ptr(x), ptr(y), ptr(out), stream()),
           "pxa_axpy_rows")
     return out
@@ -306,17 +427,16 @@ def axpy_rows(c, s, x, y, out=None):
 
 def row_ratio(num, den, like, out=None):
     """out[r] = num[r] / den[r] (float64 device vectors) cast to like's dtype, on the device."""
-    num, den = require(num, "num"), require(den, "den")
-    torch = _torch()
-    assert num.dtype == torch.float64 and den.dtype == torch.float64 and num.numel() == den.numel()
-    out = torch.empty((num.numel(),), dtype=like.dtype, device=like.device) if out is None else out
+    num = require(num, "num", dtype="float64")
+    den = require(den, "den", dtype="float64", numel=num.numel())
+    out = _out(out, like, (num.numel(),))
     check(lib.pxa_row_ratio(dtcode(like), num.numel(), ptr(num), ptr(den), ptr(out), stream()), "pxa_row_ratio")
     return out
 
 
 def lincomb3(a, x, b, y, c, z, out=None):
     x, y, z = require(x), require(y), require(z)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_lincomb3(dtcode(x), x.numel(), float(a), ptr(x), float(b), ptr(y), float(c), ptr(z), ptr(out), stream()), "pxa_lincomb3")
     return out
 
@@ -324,27 +444,29 @@ def lincomb3(a, x, b, y, c, z, out=None):
 def extrapolate(a, x, y, out=None):
     """(x - y) * a + x."""
     x, y = require(x), require(y)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_extrapolate(dtcode(x), x.numel(), float(a), ptr(x), ptr(y), ptr(out), stream()), "pxa_extrapolate")
     return out
 
 
 def div(x, d, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_div(dtcode(x), x.numel(), ptr(x), float(d), ptr(out), stream()), "pxa_div")
     return out
 
 
 def add_scalar(x, s, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_add_scalar(dtcode(x), x.numel(), ptr(x), float(s), ptr(out), stream()), "pxa_add_scalar")
     return out
 
 
 def fill(out, v):
-    out = require(out)
+    if _TIMER is not None:  # (as `require`: device work outside the fused steps closes the timing window)
+        _TIMER.interrupt()
+    out = written(out)
     check(lib.pxa_fill(dtcode(out), out.numel(), float(v), ptr(out), stream()), "pxa_fill")
     return out
 
@@ -355,21 +477,21 @@ def zeros(shape, like):
 
 def mul(x, y, out=None):
     x, y = require(x), require(y)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_mul(dtcode(x), x.numel(), ptr(x), ptr(y), ptr(out), stream()), "pxa_mul")
     return out
 
 
 def clip(x, lo, hi=None, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_clip(dtcode(x), x.numel(), ptr(x), float(lo), float(hi or 0.0), int(hi is not None), ptr(out), stream()), "pxa_clip")
     return out
 
 
 def prox_l1(x, tau, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_prox_l1(dtcode(x), x.numel(), ptr(x), float(tau), ptr(out), stream()), "pxa_prox_l1")
     return out
 
@@ -377,10 +499,9 @@ def prox_l1(x, tau, out=None):
 def admm_l1_update(x, z, u, cgrad, rho_m1, thr, tau):
     """ADMM outer update (h = lam L1, K = Id) + the next CG right-hand side in one launch
     (pxa_admm_l1_update): returns (u', z', b, r0, p0, x0), views of one (6, *x.shape) buffer."""
-    x, z, u, cgrad = require(x), require(z), require(u), require(cgrad)
+    x = require(x)
     n = x.numel()
-    assert z.numel() == n and u.numel() == n and cgrad.numel() == n
-    assert z.dtype == x.dtype and u.dtype == x.dtype and cgrad.dtype == x.dtype
+    z, u, cgrad = (require(t, name, like=x, numel=n) for t, name in ((z, "z"), (u, "u"), (cgrad, "cgrad")))
     out = empty((6,) + tuple(x.shape), x)
     check(lib.pxa_admm_l1_update(dtcode(x), n, ptr(x), ptr(z), ptr(u), ptr(cgrad), float(rho_m1), float(thr),
                                  float(tau), ptr(out), stream()), "pxa_admm_l1_update")
@@ -389,28 +510,33 @@ def admm_l1_update(x, z, u, cgrad, rho_m1, thr, tau):
 
 def fenchel_prox_l1(x, sigma, lam, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_fenchel_prox_l1(dtcode(x), x.numel(), ptr(x), float(sigma), float(lam), ptr(out), stream()), "pxa_fenchel_prox_l1")
     return out
 
 
 def moreau_grad_l1(x, mu, scale, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_moreau_grad_l1(dtcode(x), x.numel(), ptr(x), float(mu), float(scale), ptr(out), stream()), "pxa_moreau_grad_l1")
     return out
 
 
+def _grouped(x, outer, group, inner):
+    """x of an (outer, group, inner) kernel, which reads outer * group * inner elements."""
+    return require(x, "x", numel=int(outer) * int(group) * int(inner))
+
+
 def prox_l21(x, tau, outer, group, inner, out=None):
-    x = require(x)
-    out = empty_like(x) if out is None else out
+    x = _grouped(x, outer, group, inner)
+    out = _out(out, x)
     check(lib.pxa_prox_l21(dtcode(x), outer, group, inner, ptr(x), float(tau), ptr(out), stream()), "pxa_prox_l21")
     return out
 
 
 def fenchel_prox_l21(x, sigma, lam, outer, group, inner, out=None):
-    x = require(x)
-    out = empty_like(x) if out is None else out
+    x = _grouped(x, outer, group, inner)
+    out = _out(out, x)
     check(
         lib.pxa_fenchel_prox_l21(dtcode(x), outer, group, inner, ptr(x), float(sigma), float(lam), ptr(out), stream()),
         "pxa_fenchel_prox_l21",
@@ -419,8 +545,8 @@ def fenchel_prox_l21(x, sigma, lam, outer, group, inner, out=None):
 
 
 def moreau_grad_l21(x, mu, scale, outer, group, inner, out=None):
-    x = require(x)
-    out = empty_like(x) if out is None else out
+    x = _grouped(x, outer, group, inner)
+    out = _out(out, x)
     check(
         lib.pxa_moreau_grad_l21(dtcode(x), outer, group, inner, ptr(x), float(mu), float(scale), ptr(out), stream()),
         "pxa_moreau_grad_l21",
@@ -429,7 +555,7 @@ def moreau_grad_l21(x, mu, scale, outer, group, inner, out=None):
 
 
 def group_norm(x, outer, group, inner):
-    x = require(x)
+    x = _grouped(x, outer, group, inner)
     out = empty((outer * inner,), x)
     check(lib.pxa_group_norm(dtcode(x), outer, group, inner, ptr(x), ptr(out), stream()), "pxa_group_norm")
     return out
@@ -466,7 +592,7 @@ def concat_cols(parts, out=None):
     parts = [require(p) for p in parts]
     lead = parts[0].shape[:-1]
     total = sum(p.shape[-1] for p in parts)
-    out = empty((*lead, total), parts[0]) if out is None else out
+    out = _out(out, parts[0], (*lead, total), apart=parts)
     rows = out.numel() // max(total, 1)
     off = 0
     for p in parts:
@@ -477,7 +603,7 @@ def concat_cols(parts, out=None):
 
 def unary(op, x, out=None):
     x = require(x)
-    out = empty_like(x) if out is None else out
+    out = _out(out, x)
     check(lib.pxa_unary(dtcode(x), int(op), x.numel(), ptr(x), ptr(out), stream()), "pxa_unary")
     return out
 
@@ -485,36 +611,23 @@ def unary(op, x, out=None):
 def binary(op, x, y, out=None, like=None):
     """out = op(x, y); x / y device arrays of one shape or Python scalars (broadcast)."""
     xa = None if np.isscalar(x) else require(x, "x")
-    ya = None if np.isscalar(y) else require(y, "y")
+    ya = None if np.isscalar(y) else require(y, "y", like=xa, shape=None if xa is None else xa.shape)
     ref = xa if xa is not None else (ya if ya is not None else like)
-    if xa is not None and ya is not None:
-        assert xa.shape == ya.shape and xa.dtype == ya.dtype, "binary: shapes / dtypes differ"
-    out = empty_like(ref) if out is None else out
-    check(lib.pxa_binary(dtcode(ref), int(op), ref.numel(), ptr(xa) if xa is not None else None,
-                         float(x) if xa is None else 0.0, ptr(ya) if ya is not None else None,
+    out = _out(out, ref)
+    check(lib.pxa_binary(dtcode(ref), int(op), ref.numel(), _p(xa), float(x) if xa is None else 0.0, _p(ya),
                          float(y) if ya is None else 0.0, ptr(out), stream()), "pxa_binary")
     return out
 
 
 def where(cond, x, y, like=None):
-    torch = _torch()
     cond = require_bool(cond)
-    xa = None if np.isscalar(x) else require(x, "x")
-    ya = None if np.isscalar(y) else require(y, "y")
+    xa = None if np.isscalar(x) else require(x, "x", numel=cond.numel())
+    ya = None if np.isscalar(y) else require(y, "y", like=xa, numel=cond.numel())
     ref = xa if xa is not None else (ya if ya is not None else like)
     out = empty(cond.shape, ref)
-    assert out.numel() == cond.numel()
-    check(lib.pxa_where(dtcode(ref), out.numel(), cond.data_ptr(), ptr(xa) if xa is not None else None,
-                        float(x) if xa is None else 0.0, ptr(ya) if ya is not None else None,
+    check(lib.pxa_where(dtcode(ref), out.numel(), cond.data_ptr(), _p(xa), float(x) if xa is None else 0.0, _p(ya),
                         float(y) if ya is None else 0.0, ptr(out), stream()), "pxa_where")
     return out
-
-
-def require_bool(c):
-    torch = _torch()
-    if not (hasattr(c, "is_cuda") and c.is_cuda and c.dtype == torch.bool):
-        raise TypeError("pyxu_amd: condition must be a boolean device tensor")
-    return c if c.is_contiguous() else c.contiguous()
 
 
 def isnan(x):
@@ -543,7 +656,11 @@ def cast(x, dtype_like):
 
 
 def set_diag(out, rows, ld, off, value):
-    check(lib.pxa_set_diag(dtcode(out), int(rows), int(ld), int(off), float(value), ptr(out), stream()), "pxa_set_diag")
+    rows, ld, off = int(rows), int(ld), int(off)
+    if min(rows, ld, off) < 0:
+        raise ValueError(f"pyxu_amd: set_diag needs rows, ld, off >= 0, got {(rows, ld, off)}.")
+    written(out, at_least=(rows - 1) * (ld + 1) + off + 1 if rows else 0)  # the last element it sets
+    check(lib.pxa_set_diag(dtcode(out), rows, ld, off, float(value), ptr(out), stream()), "pxa_set_diag")
     return out
 
 
@@ -570,19 +687,17 @@ def relerr_stats(x, x_prev, out, copy=True):
     """RelError statistics in one pass (pxa_relerr_stats): out[0] = sum (x - x_prev)^2 and
     out[1] = sum x_prev^2 per row (out: contiguous float64 (2, rows) buffer, device or pinned host);
     returns the copy of x the criterion keeps (or None with copy=False)."""
-    torch = _torch()
     x = require(x)
-    x_prev = require(x_prev)
-    assert x_prev.shape == x.shape and x_prev.dtype == x.dtype
+    x_prev = require(x_prev, "x_prev", like=x, shape=x.shape)
     n = x.shape[-1] if x.ndim > 0 else 1
     rows = x.numel() // max(n, 1) if x.numel() else 0
-    assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == 2 * max(rows, 1)
-    assert 0 < rows <= 65535, "relerr_stats: rows out of range (use row_reduce)"
+    written(out, "out", dtype="float64", numel=2 * max(rows, 1), pinned=True)
+    if not 0 < rows <= 65535:
+        raise ValueError(f"relerr_stats: rows must be in [1, 65535], got {rows} (use row_reduce)")
     xc = empty_like(x) if copy else None
-    wsz = int(lib.pxa_relerr_stats_workspace_bytes(rows, n))
-    work = torch.empty((max(wsz // 8, 1),), dtype=torch.float64, device=x.device)
-    check(lib.pxa_relerr_stats(dtcode(x), rows, n, ptr(x), ptr(x_prev), ptr(xc) if copy else None, out.data_ptr(),
-                               ptr(work), stream()), "pxa_relerr_stats")
+    work = _workspace("pxa_relerr_stats_workspace_bytes", x, rows, n, f64=True)
+    check(lib.pxa_relerr_stats(dtcode(x), rows, n, ptr(x), ptr(x_prev), _p(xc), out.data_ptr(), ptr(work), stream()),
+          "pxa_relerr_stats")
     return xc
 
 
@@ -593,11 +708,7 @@ def cg_update(x, r, p, ap, rr, rr_out, rr_host, work, have_pap=False):
     pinned host tensor, or None.  have_pap: `work` already holds the <p, A p> partials (pxa_cg_update_tail;
     dense_normal(..., pdot=work) wrote them with A p)."""
     rows, n = x.shape
-    seq, vp_, fp_ = 0, None, None
-    if isinstance(rr_host, HostFlagBuffer):
-        seq, vp_, fp_ = rr_host.next_seq(), rr_host.vptr, rr_host.fptr
-    elif rr_host is not None:
-        vp_ = rr_host.data_ptr()
+    seq, vp_, fp_ = _publication(rr_host)
     fn = lib.pxa_cg_update_tail if have_pap else lib.pxa_cg_update
     check(fn(dtcode(x), rows, n, ptr(x), ptr(r), ptr(p), ptr(ap), rr.data_ptr(), rr_out.data_ptr(), vp_, fp_, seq,
              work.data_ptr(), stream()), "pxa_cg_update")
@@ -605,7 +716,7 @@ def cg_update(x, r, p, ap, rr, rr_out, rr_host, work, have_pap=False):
 
 
 def cg_update_xr(x, r, p, ap, rr, work):
-    """pxa_cg_update_xr: x += alpha p, r -= alpha A p and the ||r'||^2 partials (work + rows * 64 doubles), with the
+    """pxa_cg_update_xr: x += alpha p, r -= alpha A p and the ||r'||^2 partials (work + rows * _CG_BLOCKS doubles), with the
     <p, A p> partials already in `work` (dense_normal(..., pdot=work)); the p update is left to the next
     dense_normal_pfold."""
     rows, n = x.shape
@@ -618,56 +729,85 @@ def krylov_chunk(like):
     return int(lib.pxa_krylov_chunk(dtcode(like)))
 
 
+_KRYLOV_WORK = {}  # (j, n) -> doubles of pxa_krylov_workspace_bytes: a Lanczos solve asks once per basis size
+
+
+def _krylov_doubles(j, n):
+    need = _KRYLOV_WORK.get((j, n))
+    if need is None:
+        if len(_KRYLOV_WORK) > 256:
+            _KRYLOV_WORK.clear()
+        need = _KRYLOV_WORK[(j, n)] = _workspace_bytes("pxa_krylov_workspace_bytes", j, n) // 8
+    return need
+
+
 def krylov_workspace(j, n, like):
     """Workspace of pxa_krylov_dots / pxa_krylov_update for up to j rows of n (float64 device tensor)."""
-    wsz = int(lib.pxa_krylov_workspace_bytes(int(j), int(n)))
-    return _torch().zeros((max(wsz // 8, 2),), dtype=_torch().float64, device=like.device)
+    return _torch().zeros((max(_krylov_doubles(int(j), int(n)), 2),), dtype=_torch().float64, device=like.device)
 
 
-def _krylov_rows(V, j, w):
-    """(ldv, n) of the first j rows of V, a (rows, n) tensor or view with unit column stride, against w (n,)."""
+def _krylov_basis(V, j, w, work):
+    """(ldv, n) of the first j rows of V, a (rows, n) tensor or view with unit column stride, against the flat device
+    vector w (n,) the kernels read as it is; `work` from krylov_workspace."""
+    _operand(w, "w", None, None, None, None, "the Krylov step")
+    _operand(V, "V", None, w, None, None, "the Krylov step")
     n = w.numel()
-    assert V.ndim == 2 and V.shape[0] >= j and V.shape[1] == n and V.stride(1) == 1 and V.dtype == w.dtype
-    assert w.is_cuda and V.is_cuda and (w.ndim == 1 and (n == 1 or w.stride(0) == 1))
+    if not (w.ndim == 1 and w.is_contiguous()):
+        raise ValueError("pyxu_amd: `w` must be a contiguous vector")
+    if not (V.ndim == 2 and V.shape[0] >= j and V.shape[1] == n and V.stride(1) == 1):
+        raise ValueError(f"pyxu_amd: `V` of shape {tuple(V.shape)} does not hold {j} unit-stride rows of {n} entries")
+    written(work, "work", dtype="float64", at_least=_krylov_doubles(int(j), n))
     return (V.stride(0) if V.shape[0] > 1 else n), n
 
 
 def krylov_dots(V, j, w, c_out, work, scale=None):
     """pxa_krylov_dots: c_out[i] = scale * <V[i], w>, i < j (float64 device vector); scale: float64 device scalar."""
-    ldv, n = _krylov_rows(V, j, w)
-    check(lib.pxa_krylov_dots(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), ptr(scale) if scale is not None else None,
-                              ptr(c_out), ptr(work), stream()), "pxa_krylov_dots")
+    ldv, n = _krylov_basis(V, j, w, work)
+    written(c_out, "c_out", dtype="float64", at_least=int(j))
+    if scale is not None:
+        scale = require(scale, "scale", dtype="float64")
+    check(lib.pxa_krylov_dots(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), _p(scale), ptr(c_out), ptr(work), stream()),
+          "pxa_krylov_dots")
     return c_out
 
 
 def krylov_update(V, j, w, c, w_out, work, c_next=None, nrm2_out=None):
     """pxa_krylov_update: w_out = w - sum_i c[i] V[i] (w_out may be w), c_next[i] = <V[i], w_out> and nrm2_out =
     ||w_out||^2 when given (float64 device)."""
-    ldv, n = _krylov_rows(V, j, w)
-    assert w_out.dtype == w.dtype and w_out.numel() == n
-    check(lib.pxa_krylov_update(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), ptr(c), ptr(w_out),
-                                ptr(c_next) if c_next is not None else None,
-                                ptr(nrm2_out) if nrm2_out is not None else None, ptr(work), stream()), "pxa_krylov_update")
+    ldv, n = _krylov_basis(V, j, w, work)
+    c = require(c, "c", dtype="float64")
+    written(w_out, "w_out", like=w, numel=n)
+    if c_next is not None:
+        written(c_next, "c_next", dtype="float64", at_least=int(j), apart=(c,))
+    if nrm2_out is not None:
+        written(nrm2_out, "nrm2_out", dtype="float64", at_least=1)
+    check(lib.pxa_krylov_update(dtcode(w), int(j), n, ptr(V), ldv, ptr(w), ptr(c), ptr(w_out), _p(c_next), _p(nrm2_out),
+                                ptr(work), stream()), "pxa_krylov_update")
     return w_out
 
 
 def krylov_normalize(x, nrm2, out):
-    """pxa_krylov_normalize: out = x / sqrt(nrm2) with nrm2 a float64 device scalar (a zero row for nrm2 == 0)."""
+    """pxa_krylov_normalize: out = x / sqrt(nrm2) with nrm2 a float64 device scalar (a zero row for nrm2 == 0); out
+    may be x."""
+    x = require(x, "x")
+    nrm2 = require(nrm2, "nrm2", dtype="float64")
+    written(out, "out", like=x, numel=x.numel())
     check(lib.pxa_krylov_normalize(dtcode(x), x.numel(), ptr(x), ptr(nrm2), ptr(out), stream()), "pxa_krylov_normalize")
     return out
 
 
-NLCG_FR, NLCG_PR = 0, 1  # pxa_nlcg_direction variants
-_CG_BLOCKS = 64  # partials per row of the CG / NLCG tail partition (csrc/common.hpp kCgBlocks)
+# (the integer constants below mirror include/pyxu_amd.h's PXA_* #defines; tests/test_abi_table.py compares them)
+NLCG_FR, NLCG_PR = 0, 1  # PXA_NLCG_*: pxa_nlcg_direction variants
+_CG_BLOCKS = 64  # PXA_CG_BLOCKS: partials per row and plane of the CG / NLCG workspaces (layouts: include/pyxu_amd.h)
 
 
 def nlcg_blocks(n):
-    """Partials per row that pxa_nlcg_direction leaves for pxa_ls_armijo: min(64, ceil(n / 256))."""
+    """Partials per row that pxa_nlcg_direction leaves for pxa_ls_armijo: min(PXA_CG_BLOCKS, ceil(n / 256))."""
     return min(_CG_BLOCKS, (int(n) + 255) // 256)
 
 
 def nlcg_gp_partials(work, rows):
-    """The <g1, p_new> partials plane of a pxa_nlcg_direction workspace (float64 device tensor `work`)."""
+    """The <g1, p_new> partials of a pxa_nlcg_direction workspace (float64 device tensor `work`): its third plane."""
     return work[2 * rows * _CG_BLOCKS: 3 * rows * _CG_BLOCKS]
 
 
@@ -678,43 +818,28 @@ def nlcg_direction(variant, restart, g1, g0, p, p_new, gg0, gg_out, gg_host, wor
     HostFlagBuffer(rows, rows, rows): returns the publication's sequence number; a pinned tensor; or None).
     `work`: float64 device tensor of pxa_nlcg_workspace_bytes(rows) bytes; nlcg_gp_partials(work, rows) then
     holds the <g1, p_new> partials."""
-    torch = _torch()
-    g1, p = require(g1, "g1"), require(p, "p")
-    if not require(p_new, "p_new") is p_new:
-        raise ValueError("nlcg_direction: p_new is written in place and must be contiguous")
-    if g1.dim() != 2 or p.shape != g1.shape or p_new.shape != g1.shape or p.dtype != g1.dtype or p_new.dtype != g1.dtype:
+    ctx = "nlcg_direction"
+    g1 = require(g1, "g1", ctx=ctx)
+    if g1.dim() != 2:
         raise ValueError("nlcg_direction: g1, p and p_new must be (rows, n) tensors of one dtype")
     rows, n = g1.shape
     if not (1 <= rows <= 65535 and n >= 1):
         raise ValueError(f"nlcg_direction: rows must be in [1, 65535] and n >= 1, got {(rows, n)}")
     if variant not in (NLCG_FR, NLCG_PR):
         raise ValueError(f"nlcg_direction: unknown variant {variant}")
+    p = require(p, "p", like=g1, shape=g1.shape, ctx=ctx)
     if g0 is not None:
-        g0 = require(g0, "g0")
-        if g0.shape != g1.shape or g0.dtype != g1.dtype:
-            raise ValueError("nlcg_direction: g0 must match g1")
+        g0 = require(g0, "g0", like=g1, shape=g1.shape, ctx=ctx)
     elif variant == NLCG_PR and not restart:
         raise ValueError("nlcg_direction: the PR variant needs g0")
-    if p_new.data_ptr() in (p.data_ptr(), g1.data_ptr()):
-        raise ValueError("nlcg_direction: p_new must not alias p or g1")
-    for t, name in ((gg0, "gg0"), (gg_out, "gg_out")):
-        if t.dtype != torch.float64 or t.numel() != rows or not t.is_contiguous() or not t.is_cuda:
-            raise ValueError(f"nlcg_direction: {name} must be a contiguous float64 device vector of {rows} entries")
-    if gg_out.data_ptr() == gg0.data_ptr():
-        raise ValueError("nlcg_direction: gg_out must not be gg0")
-    need = int(lib.pxa_nlcg_workspace_bytes(rows))
-    if work.dtype != torch.float64 or not work.is_cuda or work.numel() * 8 < need:
-        raise ValueError(f"nlcg_direction: work must be a float64 device tensor of >= {need} bytes")
-    seq, vp_, fp_ = 0, None, None
-    if isinstance(gg_host, HostFlagBuffer):
-        if len(gg_host.values) < rows or len(gg_host.flags) != rows:
-            raise ValueError("nlcg_direction: the HostFlagBuffer must hold rows values and rows flags")
-        seq, vp_, fp_ = gg_host.next_seq(), gg_host.vptr, gg_host.fptr
-    elif gg_host is not None:
-        vp_ = gg_host.data_ptr()
-    check(lib.pxa_nlcg_direction(dtcode(g1), int(variant), int(bool(restart)), rows, n, ptr(g1),
-                                 ptr(g0) if g0 is not None else None, ptr(p), ptr(p_new), gg0.data_ptr(),
-                                 gg_out.data_ptr(), vp_, fp_, seq, work.data_ptr(), stream()), "pxa_nlcg_direction")
+    written(p_new, "p_new", like=g1, numel=rows * n, apart=(p, g1), ctx=ctx)
+    gg0 = require(gg0, "gg0", dtype="float64", numel=rows, ctx=ctx)
+    written(gg_out, "gg_out", dtype="float64", numel=rows, apart=(gg0,), ctx=ctx)
+    written(work, "work", dtype="float64", at_least=_workspace_bytes("pxa_nlcg_workspace_bytes", rows) // 8, ctx=ctx)
+    seq, vp_, fp_ = _publication(gg_host, "gg_host", rows)
+    check(lib.pxa_nlcg_direction(dtcode(g1), int(variant), int(bool(restart)), rows, n, ptr(g1), _p(g0), ptr(p),
+                                 ptr(p_new), gg0.data_ptr(), gg_out.data_ptr(), vp_, fp_, seq, work.data_ptr(), stream()),
+          "pxa_nlcg_direction")
     return seq
 
 
@@ -724,25 +849,19 @@ def ls_armijo(f_trial, f_x, gp, nb, c, r, a, trials, fb):
     per row (nb > 0, as nlcg_gp_partials) or one folded value per row (nb == 0); trials: int32 device (rows,),
     incremented on failing rows; fb: a HostFlagBuffer(1, 1, 1) that receives the number of failing rows
     (ls_failed(fb, seq) reads it).  Returns the publication's sequence number."""
-    torch = _torch()
-    f_trial, f_x = require(f_trial, "f_trial"), require(f_x, "f_x")
-    if not require(a, "a") is a:
-        raise ValueError("ls_armijo: a is updated in place and must be contiguous")
+    ctx = "ls_armijo"
+    written(a, "a", ctx=ctx)
     rows = a.numel()
     if not 1 <= rows <= 65535:
         raise ValueError(f"ls_armijo: rows must be in [1, 65535], got {rows}")
-    if f_trial.numel() != rows or f_x.numel() != rows or f_trial.dtype != a.dtype or f_x.dtype != a.dtype:
-        raise ValueError("ls_armijo: f_trial, f_x and a must hold one value per row in one dtype")
+    f_trial = require(f_trial, "f_trial", like=a, numel=rows, ctx=ctx)
+    f_x = require(f_x, "f_x", like=a, numel=rows, ctx=ctx)
     nb = int(nb)
     if not 0 <= nb <= _CG_BLOCKS:
         raise ValueError(f"ls_armijo: nb must be in [0, {_CG_BLOCKS}], got {nb}")
-    if gp.dtype != torch.float64 or not gp.is_cuda or not gp.is_contiguous() or gp.numel() < rows * max(nb, 1):
-        raise ValueError("ls_armijo: gp must be a contiguous float64 device tensor of rows * max(nb, 1) entries")
-    if trials.dtype != torch.int32 or not trials.is_cuda or not trials.is_contiguous() or trials.numel() != rows:
-        raise ValueError("ls_armijo: trials must be a contiguous int32 device vector of `rows` entries")
-    if not isinstance(fb, HostFlagBuffer) or len(fb.values) < 1 or len(fb.flags) != 1:
-        raise ValueError("ls_armijo: fb must be a HostFlagBuffer(1, 1, 1)")
-    seq = fb.next_seq()
+    written(gp, "gp", dtype="float64", at_least=rows * max(nb, 1), ctx=ctx)  # (read only, but taken as it is: a view)
+    written(trials, "trials", dtype="int32", numel=rows, ctx=ctx)
+    seq = flag_buffer(fb, "fb", 1, 1).next_seq()
     check(lib.pxa_ls_armijo(dtcode(a), rows, ptr(f_trial), ptr(f_x), gp.data_ptr(), nb, float(c), float(r), ptr(a),
                             trials.data_ptr(), fb.vptr, fb.fptr, seq, stream()), "pxa_ls_armijo")
     return seq
@@ -754,8 +873,9 @@ def ls_failed(fb, seq):
     return int(fb.values.view(np.uint32)[0])
 
 
-PROXADAM_VARIANTS = {"adam": 0, "amsgrad": 1, "padam": 2}  # pxa_proxadam_moments variants
-PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX = 1, 2, 3, 4  # pxa_proxadam_sub_step prox kinds
+PROXADAM_VARIANTS = {"adam": 0, "amsgrad": 1, "padam": 2}  # PXA_PROXADAM_*: pxa_proxadam_moments variants
+PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX = 1, 2, 3, 4  # PXA_PROX_*: element-wise prox kinds
+_PROXADAM_PLANES = 5  # planes of rows * nb doubles that open a ProxAdam workspace (layout: include/pyxu_amd.h)
 
 
 def proxadam_blocks(rows, n):
@@ -765,37 +885,28 @@ def proxadam_blocks(rows, n):
 
 def proxadam_workspace(rows, n, like):
     """A float64 device tensor of pxa_proxadam_workspace_bytes(rows, n) bytes."""
-    need = int(lib.pxa_proxadam_workspace_bytes(int(rows), int(n)))
-    return _torch().empty(((need + 7) // 8,), dtype=_torch().float64, device=like.device)
+    return _workspace("pxa_proxadam_workspace_bytes", like, int(rows), int(n), f64=True)
 
 
 def proxadam_work_views(work, rows, n):
     """(psi partial maxima (rows, nb), psimax (rows,), state words int32 (rows,)) of a ProxAdam workspace."""
-    nb = proxadam_blocks(rows, n)
-    tail = work[5 * rows * nb + rows:].view(_torch().int32)
-    return work[: rows * nb].reshape(rows, nb), work[5 * rows * nb: 5 * rows * nb + rows], tail[:rows]
+    plane = rows * proxadam_blocks(rows, n)
+    psimax = _PROXADAM_PLANES * plane
+    tail = work[psimax + rows:].view(_torch().int32)
+    return work[:plane].reshape(rows, -1), work[psimax: psimax + rows], tail[:rows]
 
 
 def proxadam_stat_partials(work, rows, n, k):
-    """The (2, rows, nb) partials sum (z_new - z)^2 / sum z^2 that sub-step launch `k` left."""
-    nb = proxadam_blocks(rows, n)
-    off = rows * nb * (1 + 2 * (k & 1))
-    return work[off: off + 2 * rows * nb].reshape(2, rows, nb)
+    """The (2, rows, nb) partials sum (z_new - z)^2 / sum z^2 that sub-step launch `k` left: the pair of planes
+    behind the psi maxima's for even k, the next pair for odd k."""
+    plane = rows * proxadam_blocks(rows, n)
+    off = plane * (1 + 2 * (k & 1))
+    return work[off: off + 2 * plane].reshape(2, rows, -1)
 
 
-def _proxadam_operand(t, name, rows, n, like):
-    """A contiguous (rows, n) device operand of like's dtype, taken as it is (views may start off a 16-byte
-    boundary: the kernels then take their scalar path)."""
-    if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dtype == like.dtype
-            and tuple(t.shape) == (rows, n)):
-        raise ValueError(f"proxadam: {name} must be a contiguous ({rows}, {n}) device tensor of dtype {like.dtype}")
-    return t
-
-
-def _proxadam_work_check(work, rows, n, where):
-    need = int(lib.pxa_proxadam_workspace_bytes(rows, n))
-    if work.dtype != _torch().float64 or not work.is_cuda or not work.is_contiguous() or work.numel() * 8 < need:
-        raise ValueError(f"{where}: work must be a contiguous float64 device tensor of >= {need} bytes")
+def _proxadam_work(work, rows, n, ctx):
+    return written(work, "work", dtype="float64", ctx=ctx,
+                   at_least=(_workspace_bytes("pxa_proxadam_workspace_bytes", rows, n) + 7) // 8)
 
 
 def proxadam_moments(variant, first, g, m, v, vhat, x, m_out, v_out, vhat_out, x_out, b1, omb1, b2, omb2, eps_var, c1,
@@ -816,24 +927,19 @@ def proxadam_moments(variant, first, g, m, v, vhat, x, m_out, v_out, vhat_out, x
         ops["vhat"] = vhat
     if psi_out is not None:
         ops["psi_out"] = psi_out
-    for name, t in ops.items():
+    for name, t in ops.items():  # (every operand as it is, inputs too: the solver passes views of one state buffer)
         if t is None:
             raise ValueError(f"proxadam_moments: {name} is missing")
-        _proxadam_operand(t, name, rows, n, g)
-    others = [t.data_ptr() for k, t in ops.items() if k != "x_out"]
-    if x_out.data_ptr() in others:
-        raise ValueError("proxadam_moments: x_out must not alias another operand")
+        written(t, name, like=g, numel=rows * n, ctx="proxadam_moments",
+                apart=[o for k, o in ops.items() if k != name] if name in ("x_out", "psi_out") else ())
     if psi_out is not None:
-        if psi_out.data_ptr() in [t.data_ptr() for k, t in ops.items() if k != "psi_out"]:
-            raise ValueError("proxadam_moments: psi_out must not alias another operand")
         if work is None:
             raise ValueError("proxadam_moments: psi_out needs the workspace")
-        _proxadam_work_check(work, rows, n, "proxadam_moments")
+        _proxadam_work(work, rows, n, "proxadam_moments")
     check(lib.pxa_proxadam_moments(dtcode(g), int(variant), int(bool(first)), rows, n, float(b1), float(omb1), float(b2),
                                    float(omb2), float(eps_var), float(c1), float(c2), float(eps_adam), float(a), float(p),
-                                   ptr(g), ptr(m), ptr(v), ptr(vhat) if vhat is not None else None, ptr(x), ptr(m_out),
-                                   ptr(v_out), ptr(vhat_out), ptr(x_out), ptr(psi_out) if psi_out is not None else None,
-                                   work.data_ptr() if work is not None else None, stream()), "pxa_proxadam_moments")
+                                   ptr(g), ptr(m), ptr(v), _p(vhat), ptr(x), ptr(m_out), ptr(v_out), ptr(vhat_out),
+                                   ptr(x_out), _p(psi_out), _p(work), stream()), "pxa_proxadam_moments")
     return x_out
 
 
@@ -843,7 +949,7 @@ def proxadam_sub_init(rows, n, work):
     rows, n = int(rows), int(n)
     if not (1 <= rows <= 65535 and n >= 1):
         raise ValueError(f"proxadam_sub_init: rows must be in [1, 65535] and n >= 1, got {(rows, n)}")
-    _proxadam_work_check(work, rows, n, "proxadam_sub_init")
+    _proxadam_work(work, rows, n, "proxadam_sub_init")
     check(lib.pxa_proxadam_sub_init(rows, n, work.data_ptr(), stream()), "pxa_proxadam_sub_init")
 
 
@@ -861,14 +967,10 @@ def proxadam_sub_step(kind, k, mom, eps, a, pw, xt, psi, z_prev, z, z_new, out, 
         raise ValueError(f"proxadam_sub_step: rows must be in [1, 65535], n >= 1 and k >= 1, got {(rows, n, k)}")
     ops = dict(xt=xt, psi=psi, z_prev=z_prev, z=z, z_new=z_new, out=out)
     for name, t in ops.items():
-        _proxadam_operand(t, name, rows, n, xt)
-    for name in ("z_new", "out"):
-        if ops[name].data_ptr() in [t.data_ptr() for q, t in ops.items() if q != name]:
-            raise ValueError(f"proxadam_sub_step: {name} must not alias another operand")
-    _proxadam_work_check(work, rows, n, "proxadam_sub_step")
-    if not isinstance(fb, HostFlagBuffer) or len(fb.values) < 1 or len(fb.flags) != 1:
-        raise ValueError("proxadam_sub_step: fb must be a HostFlagBuffer(1, 1, 1)")
-    seq = fb.next_seq()
+        written(t, name, like=xt, numel=rows * n, ctx="proxadam_sub_step",
+                apart=[o for q, o in ops.items() if q != name] if name in ("z_new", "out") else ())
+    _proxadam_work(work, rows, n, "proxadam_sub_step")
+    seq = flag_buffer(fb, "fb", 1, 1).next_seq()
     check(lib.pxa_proxadam_sub_step(dtcode(xt), int(kind), int(k), rows, n, float(mom), float(eps), float(a), float(pw),
                                     ptr(xt), ptr(psi), ptr(z_prev), ptr(z), ptr(z_new), ptr(out), work.data_ptr(),
                                     fb.vptr, fb.fptr, seq, stream()), "pxa_proxadam_sub_step")
@@ -882,20 +984,9 @@ def proxadam_running(fb, seq):
 
 
 # ------------------------------------------------------------------ Langevin samplers (csrc/sampler.hip)
-_U64 = (1 << 64) - 1
-
-
-def _flat_operand(t, name, n, like):
-    """A contiguous device operand of n elements of like's dtype, taken as it is (a view may start off a 16-byte
-    boundary: the kernels then go element by element)."""
-    if not (hasattr(t, "is_cuda") and t.is_cuda and t.is_contiguous() and t.dtype == like.dtype and t.numel() == n):
-        raise ValueError(f"sampler: {name} must be a contiguous device tensor of {n} elements of dtype {like.dtype}")
-    return t
-
-
 def _counter(v, name):
     v = int(v)
-    if not 0 <= v <= _U64:
+    if v < 0 or v >> 64:
         raise ValueError(f"sampler: {name} must fit 64 unsigned bits, got {v}")
     return v
 
@@ -903,8 +994,7 @@ def _counter(v, name):
 def philox_normal(out, seed, step, e0=0):
     """pxa_philox_normal: out (flat) = the standard normals of global elements e0 .. e0 + out.numel() - 1 of the
     stream (seed, step) (include/pyxu_amd.h)."""
-    dtcode(out)
-    _flat_operand(out, "out", out.numel(), out)
+    written(out)
     check(lib.pxa_philox_normal(dtcode(out), out.numel(), _counter(seed, "seed"), _counter(step, "step"),
                                 _counter(e0, "e0"), ptr(out), stream()), "pxa_philox_normal")
     return out
@@ -916,20 +1006,17 @@ def langevin_step(kind, gamma, lam, pw, x, grad, x_out, noise=None, seed=0, step
     may be x."""
     if kind not in (0, PROX_L1, PROX_POS, PROX_POSL1, PROX_BOX):
         raise ValueError(f"langevin_step: unknown kind {kind}")
-    dtcode(x)
+    written(x, "x", ctx="langevin_step")  # (inputs as they are too: the samplers pass views of their chain state)
     n = x.numel()
-    ops = dict(x=x, grad=grad, x_out=x_out)
+    written(grad, "grad", like=x, numel=n, ctx="langevin_step")
     if noise is not None:
-        ops["noise"] = noise
-    for name, t in ops.items():
-        _flat_operand(t, name, n, x)
-    if x_out.data_ptr() in [t.data_ptr() for k, t in ops.items() if k not in ("x", "x_out")]:
-        raise ValueError("langevin_step: x_out may alias x only")
+        written(noise, "noise", like=x, numel=n, ctx="langevin_step")
+    written(x_out, "x_out", like=x, numel=n, apart=(grad, noise), ctx="langevin_step")  # (x_out may be x)
     if not float(gamma) > 0 or (kind != 0 and not float(lam) > 0):
         raise ValueError(f"langevin_step: gamma and lam must be positive, got {(gamma, lam)}")
     check(lib.pxa_langevin_step(dtcode(x), int(kind), n, float(gamma), float(lam), float(pw), _counter(seed, "seed"),
                                 _counter(step, "step"), _counter(e0, "e0"), ptr(x), ptr(grad),
-                                ptr(noise) if noise is not None else None, ptr(x_out), stream()), "pxa_langevin_step")
+                                _p(noise), ptr(x_out), stream()), "pxa_langevin_step")
     return x_out
 
 
@@ -937,15 +1024,10 @@ def online_moments(order, k, x, mean, sums):
     """pxa_online_moments: sample number k (0-based) folded into mean (x's dtype) and sums ((order - 1, n) float64)."""
     if order not in (2, 3, 4) or int(k) < 0:
         raise ValueError(f"online_moments: order must be 2, 3 or 4 and k >= 0, got {(order, k)}")
-    dtcode(x)
+    written(x, "x", ctx="online_moments")  # (as it is: a view of the sampler's chain state)
     n = x.numel()
-    _flat_operand(x, "x", n, x)
-    _flat_operand(mean, "mean", n, x)
-    if not (hasattr(sums, "is_cuda") and sums.is_cuda and sums.is_contiguous() and sums.dtype == _torch().float64
-            and sums.numel() == (order - 1) * n):
-        raise ValueError(f"online_moments: sums must be a contiguous float64 device tensor of {order - 1} x {n}")
-    if mean.data_ptr() == x.data_ptr():
-        raise ValueError("online_moments: mean must not alias x")
+    written(mean, "mean", like=x, numel=n, apart=(x,), ctx="online_moments")
+    written(sums, "sums", dtype="float64", numel=(order - 1) * n, apart=(x,), ctx="online_moments")
     check(lib.pxa_online_moments(dtcode(x), int(order), int(k), n, ptr(x), ptr(mean), ptr(sums), stream()),
           "pxa_online_moments")
     return mean, sums
@@ -953,15 +1035,19 @@ def online_moments(order, k, x, mean, sums):
 
 def dense_normal_pfold(A, r, p, p_new, rr, rr_out, fb, seq, s, d, work, pdot):
     """pxa_dense_normal_pdot_pfold: p_new = r + beta p (the CG's previous p update, beta from cg_update_xr's ||r'||^2
-    partials at pdot + 64 doubles and `rr`), then Y = s A^T (A p_new) + d p_new and the <p_new, Y> partials into
-    pdot; ||r'||^2 into rr_out (device) and HostFlagBuffer `fb` under publication `seq`.  Returns Y."""
+    partials in pdot's second plane, the CG workspace layout of one row, and `rr`), then Y = s A^T (A p_new) + d p_new
+    and the <p_new, Y> partials into pdot; ||r'||^2 into rr_out (device) and HostFlagBuffer `fb` under publication
+    `seq`.  Returns Y."""
     M, N = A.shape
+    if p.numel() != N:  # one right-hand side: the planes of the CG workspace hold rows * _CG_BLOCKS doubles each
+        raise ValueError(f"pxa_dense_normal_pdot_pfold: p must be a single row of {N} entries, got {tuple(p.shape)}")
     wsz = int(lib.pxa_dense_normal_workspace_bytes(dtcode(p), M, N, 1))
     if wsz == 0 or work is None or work.numel() < wsz:
         raise ValueError("pxa_dense_normal_pdot_pfold: unsupported operand or workspace")
     Y = empty(p.shape, p)
+    rr_parts = pdot.data_ptr() + _CG_BLOCKS * pdot.element_size()
     check(lib.pxa_dense_normal_pdot_pfold(dtcode(p), M, N, ptr(A), ptr(r), ptr(p), ptr(p_new), rr.data_ptr(),
-                                          pdot.data_ptr() + 64 * 8, rr_out.data_ptr(), fb.vptr, fb.fptr, int(seq),
+                                          rr_parts, rr_out.data_ptr(), fb.vptr, fb.fptr, int(seq),
                                           float(s), float(d), ptr(Y), ptr(work), pdot.data_ptr(), stream()),
           "pxa_dense_normal_pdot_pfold")
     return Y
@@ -970,7 +1056,7 @@ def dense_normal_pfold(A, r, p, p_new, rr, rr_out, fb, seq, s, d, work, pdot):
 def tile_partials_fold(parts, rows, per_row, out):
     """RelError statistics from the fused PGD step's per-tile partials (pxa_tile_partials_fold):
     out (contiguous float64 (2, rows), device or pinned host) = per-row sum (x_new - x)^2, sum x^2."""
-    assert out.is_contiguous() and out.numel() == 2 * rows
+    written(out, "out", dtype="float64", numel=2 * rows, pinned=True)
     check(lib.pxa_tile_partials_fold(int(rows), int(per_row), parts.data_ptr(), out.data_ptr(), None, 0, stream()),
           "pxa_tile_partials_fold")
     return out
@@ -1086,67 +1172,41 @@ class HostFlagBuffer:
             self._ptr = None
 
 
-def row_reduce(op, x, y=None, out=None):
-    """Per-row reduction over the last axis -> float64 device tensor of shape x.shape[:-1] (or (1,)).
-    `out`: optional contiguous float64 device buffer of max(rows, 1) elements to write into."""
-    torch = _torch()
+def _row_reduce(call, name, x, y, out):
+    """Shared body of row_reduce / row_reduce_pow: `call(dtype, rows, n, x, y, out, work, stream)` on every slab of
+    at most 65535 rows (the grid-y limit)."""
     x = require(x)
     n = x.shape[-1] if x.ndim > 0 else 1
     rows = int(np.prod(x.shape[:-1])) if x.ndim > 1 else 1  # rows of zero elements reduce to 0 (pxa_row_reduce)
     if y is not None:
-        y = require(y)
-        assert y.shape == x.shape
+        y = require(y, "y", like=x, shape=x.shape)
     if out is None:
-        out = torch.empty((max(rows, 1),), dtype=torch.float64, device=x.device)
+        out = empty_f64((max(rows, 1),), x)
     else:
-        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == max(rows, 1)
+        written(out, "out", dtype="float64", numel=max(rows, 1), apart=(x, y))
     if x.numel() == 0:  # no rows, or rows without elements: the statistic of an empty row is 0
         out.zero_()
         return out.reshape(x.shape[:-1]) if x.ndim > 1 and rows > 0 else out
-    # rows beyond the grid-y limit are processed in slabs
-    step = 65535
-    for r0 in range(0, rows, step):
-        r1 = min(rows, r0 + step)
-        es = x.element_size()
-        wsz = int(lib.pxa_row_reduce_workspace_bytes(r1 - r0, n))
-        work = torch.empty((max(wsz // 8, 1),), dtype=torch.float64, device=x.device)
-        check(
-            lib.pxa_row_reduce(
-                dtcode(x), op, r1 - r0, n, ptr(x) + r0 * n * es, (ptr(y) + r0 * n * es) if y is not None else None,
-                out.data_ptr() + r0 * 8, ptr(work), stream(),
-            ),
-            "pxa_row_reduce",
-        )
+    es = x.element_size()
+    for r0 in range(0, rows, _ROW_SLAB):
+        r1 = min(rows, r0 + _ROW_SLAB)
+        work = _workspace("pxa_row_reduce_workspace_bytes", x, r1 - r0, n, f64=True)
+        check(call(dtcode(x), r1 - r0, n, ptr(x) + r0 * n * es, (ptr(y) + r0 * n * es) if y is not None else None,
+                   out.data_ptr() + r0 * 8, ptr(work), stream()), name)
     return out.reshape(x.shape[:-1]) if x.ndim > 1 else out
+
+
+def row_reduce(op, x, y=None, out=None):
+    """Per-row reduction over the last axis -> float64 device tensor of shape x.shape[:-1] (or (1,)).
+    `out`: optional contiguous float64 device buffer of max(rows, 1) elements to write into."""
+    return _row_reduce(lambda dt, rows, n, *a: lib.pxa_row_reduce(dt, op, rows, n, *a), "pxa_row_reduce", x, y, out)
 
 
 def row_reduce_pow(p, x, y=None, out=None):
     """Per-row sum |x - y|^p (p > 0) or non-zero count (p == 0) -> float64 device tensor of shape x.shape[:-1]
     (or (1,)).  `out`: as in row_reduce."""
-    torch = _torch()
-    x = require(x)
-    n = x.shape[-1] if x.ndim > 0 else 1
-    rows = int(np.prod(x.shape[:-1])) if x.ndim > 1 else 1  # rows of zero elements reduce to 0 (pxa_row_reduce)
-    if y is not None:
-        y = require(y)
-        assert y.shape == x.shape
-    if out is None:
-        out = torch.empty((max(rows, 1),), dtype=torch.float64, device=x.device)
-    else:
-        assert out.dtype == torch.float64 and out.is_contiguous() and out.numel() == max(rows, 1)
-    if x.numel() == 0:  # no rows, or rows without elements: the statistic of an empty row is 0
-        out.zero_()
-        return out.reshape(x.shape[:-1]) if x.ndim > 1 and rows > 0 else out
-    step = 65535
-    es = x.element_size()
-    for r0 in range(0, rows, step):
-        r1 = min(rows, r0 + step)
-        wsz = int(lib.pxa_row_reduce_workspace_bytes(r1 - r0, n))
-        work = torch.empty((max(wsz // 8, 1),), dtype=torch.float64, device=x.device)
-        check(lib.pxa_row_reduce_pow(dtcode(x), r1 - r0, n, float(p), ptr(x) + r0 * n * es,
-                                     (ptr(y) + r0 * n * es) if y is not None else None, out.data_ptr() + r0 * 8,
-                                     ptr(work), stream()), "pxa_row_reduce_pow")
-    return out.reshape(x.shape[:-1]) if x.ndim > 1 else out
+    return _row_reduce(lambda dt, rows, n, *a: lib.pxa_row_reduce_pow(dt, rows, n, float(p), *a), "pxa_row_reduce_pow",
+                       x, y, out)
 
 
 # ------------------------------------------------------------------ row threshold search (csrc/threshold.hip)
@@ -1175,10 +1235,10 @@ def _threshold_stream(x2, r0, r1, a, b, c, mu, passes, batch):
     torch = _torch()
     rows, n, es = r1 - r0, x2.shape[1], x2.element_size()
     state = torch.empty((rows,), dtype=torch.int32, device=x2.device)
-    wsz = int(lib.pxa_row_threshold_workspace_bytes(rows, n))
-    work = torch.empty((max(wsz // 8, 1),), dtype=torch.float64, device=x2.device)
+    work = _workspace("pxa_row_threshold_workspace_bytes", x2, rows, n, f64=True)
     batch = THRESHOLD_FIRST_BATCH if batch is None else int(batch)
-    assert batch >= 1
+    if batch < 1:
+        raise ValueError(f"pyxu_amd: the threshold search needs batch >= 1, got {batch}.")
     total, first = 0, 1
     while True:
         check(lib.pxa_row_threshold_stream(dtcode(x2), rows, n, ptr(x2) + r0 * n * es, a, b, c, first, batch,
@@ -1228,16 +1288,14 @@ def row_threshold(x2, a, b, c, batch=None):
 def row_shrink(x2, mu, mode, out=None):
     """out[r] = sign(x) min(|x|, mu[r]) (SHRINK_CLAMP) or sign(x) max(|x| - mu[r], 0) (SHRINK_SOFT); mu: float64
     device vector of one threshold per row.  `out` may be x2 itself."""
-    torch = _torch()
-    x2, mu = require(x2), require(mu, "mu")
+    x2 = require(x2)
     if x2.ndim != 2:
         raise ValueError(f"pyxu_amd: row_shrink expects a (rows, n) array, got shape {tuple(x2.shape)}.")
     if mode not in (SHRINK_CLAMP, SHRINK_SOFT):
         raise ValueError(f"pyxu_amd: unknown shrink mode {mode!r}.")
     rows, n = x2.shape
-    assert mu.dtype == torch.float64 and mu.numel() == rows
-    out = empty_like(x2) if out is None else out
-    assert out.shape == x2.shape and out.dtype == x2.dtype and out.is_contiguous()
+    mu = require(mu, "mu", dtype="float64", numel=rows)
+    out = _out(out, x2)
     es = x2.element_size()
     for r0 in range(0, rows if n > 0 else 0, _ROW_SLAB):
         r1 = min(rows, r0 + _ROW_SLAB)
@@ -1253,13 +1311,15 @@ def row_threshold_prox(x2, a, b, c, mode, out=None, batch=None, info=False):
     x2, a, b, c = _threshold_args(x2, a, b, c)
     if mode not in (SHRINK_CLAMP, SHRINK_SOFT):
         raise ValueError(f"pyxu_amd: unknown shrink mode {mode!r}.")
-    out = empty_like(x2) if out is None else out
-    assert out.shape == x2.shape and out.dtype == x2.dtype and out.is_contiguous()
+    out = _out(out, x2)
     mu, passes, out = _threshold_run(x2, a, b, c, mode, out, batch)
     return (out, mu, passes) if info else out
 
 
 # ------------------------------------------------------------------ stencils
+_MAX_TAPS = 64  # PXA_MAX_TAPS: per-axis tap slots of pxa_stencil_sep's offsets / coefs
+
+
 def stencil_axis(x, y, stack, shape, axis, offsets, coefs, zero_partial=False, xs=None, ys=None, beta=0.0, x_off=0, y_off=0):
     """One separable-axis pass (see pxa_stencil_axis).  `x_off`/`y_off`: element offsets into x/y."""
     N = int(np.prod(shape))
@@ -1277,9 +1337,8 @@ def stencil_axis(x, y, stack, shape, axis, offsets, coefs, zero_partial=False, x
 
 def stencil_sep(x, y, stack, shape, taps, beta=0.0, xs=None, ys=None, x_off=0, y_off=0):
     """Separable constant-mode filter; taps[d] = (offsets, coefs) or None (identity axis)."""
-    torch = _torch()
     D = len(shape)
-    MT = 64
+    MT = _MAX_TAPS
     ntaps = [0 if t is None else len(t[0]) for t in taps]
     offs = [0] * (D * MT)
     cfs = [0.0] * (D * MT)
@@ -1289,14 +1348,13 @@ def stencil_sep(x, y, stack, shape, taps, beta=0.0, xs=None, ys=None, x_off=0, y
                 offs[d * MT + q] = o
                 cfs[d * MT + q] = c
     N = int(np.prod(shape))
-    wsz = int(lib.pxa_stencil_sep_workspace_bytes(dtcode(x), stack, D, i64_array(shape), int_array(ntaps)))
-    work = torch.empty((max(wsz, 1),), dtype=torch.uint8, device=x.device) if wsz else None
+    work = _workspace("pxa_stencil_sep_workspace_bytes", x, dtcode(x), stack, D, i64_array(shape), int_array(ntaps))
     es = x.element_size()
     check(
         lib.pxa_stencil_sep(
             dtcode(x), stack, D, i64_array(shape), int_array(ntaps), i32_array(offs), f64_array(cfs),
             ptr(x) + x_off * es, N if xs is None else xs, ptr(y) + y_off * es, N if ys is None else ys, float(beta),
-            ptr(work) if work is not None else None, stream(),
+            _p(work), stream(),
         ),
         "pxa_stencil_sep",
     )
@@ -1370,8 +1428,9 @@ def gather_cols(x, idx, out=None):
     x = require(x)
     n = x.shape[-1]
     rows = int(np.prod(x.shape[:-1]))
+    idx = require(idx, "idx", dtype="int64")
     m = idx.numel()
-    out = empty((*x.shape[:-1], m), x) if out is None else out
+    out = _out(out, x, (*x.shape[:-1], m), apart=(x,))
     check(lib.pxa_gather_cols(dtcode(x), rows, n, ptr(x), m, ptr(idx), ptr(out), stream()), "pxa_gather_cols")
     return out
 
@@ -1381,7 +1440,8 @@ def scatter_cols(y, idx, n, out=None):
     y = require(y)
     m = y.shape[-1]
     rows = int(np.prod(y.shape[:-1]))
-    out = empty((*y.shape[:-1], n), y) if out is None else out
+    idx = require(idx, "idx", dtype="int64", numel=m)
+    out = _out(out, y, (*y.shape[:-1], n), apart=(y,))
     check(lib.pxa_scatter_cols(dtcode(y), rows, m, ptr(y), n, ptr(idx), ptr(out), stream()), "pxa_scatter_cols")
     return out
 
@@ -1403,16 +1463,12 @@ def gradient2(x, stack, shape, dirs, o0, c0, o1, c1, adjoint=False):
 # ------------------------------------------------------------------ dense
 def dense_matmat(A, X, trans):
     """trans=0: Y = X A^T (X: (B, N)); trans=1: Y = X A (X: (B, M))."""
-    torch = _torch()
     M, N = A.shape
     B = X.shape[0]
     Y = empty((B, N if trans else M), X)
-    wsz = int(lib.pxa_dense_workspace_bytes(dtcode(X), int(trans), M, N, B))
-    work = torch.empty((max(wsz, 1),), dtype=torch.uint8, device=X.device) if wsz else None
-    check(
-        lib.pxa_dense_matmat(dtcode(X), int(trans), M, N, B, ptr(A), ptr(X), ptr(Y), ptr(work) if work is not None else None, stream()),
-        "pxa_dense_matmat",
-    )
+    work = _workspace("pxa_dense_workspace_bytes", X, dtcode(X), int(trans), M, N, B)
+    check(lib.pxa_dense_matmat(dtcode(X), int(trans), M, N, B, ptr(A), ptr(X), ptr(Y), _p(work), stream()),
+          "pxa_dense_matmat")
     return Y
 
 
@@ -1441,7 +1497,7 @@ def dense_normal(A, x, s, d, work=None, pdot=None):
         check(lib.pxa_dense_normal(dtcode(x), M, N, 1, ptr(A), ptr(x), float(s), float(d), ptr(Y), ptr(work), stream()),
               "pxa_dense_normal")
     else:
-        assert pdot.dtype == torch.float64 and pdot.is_cuda
+        written(pdot, "pdot", dtype="float64")
         check(lib.pxa_dense_normal_pdot(dtcode(x), M, N, ptr(A), ptr(x), float(s), float(d), ptr(Y), ptr(work),
                                         pdot.data_ptr(), stream()), "pxa_dense_normal_pdot")
     return Y
@@ -1462,17 +1518,8 @@ def pgd_tv2d_step(x, x_prev, hty, x_new, stack, y_images, n0, n1, taps0, taps1, 
     `partials`, the per-tile RelError statistics are taken against `x_ref` (None: against x)."""
     if pre is None:
         pre = pgd_tv2d_args(stack, y_images, n0, n1, taps0, taps1, h0, h1, lam, mu, prox, prox_w)
-    ev = _TIMER.begin() if _TIMER is not None else None  # measurement hook (bench.py), normally None
-    check(
-        lib.pxa_pgd_tv2d_step(
-            dtcode(x), *pre, float(a), float(tau), int(prox), float(prox_w),
-            x.data_ptr(), x_prev.data_ptr(), hty.data_ptr(), x_new.data_ptr(), ptr(partials) if partials is not None else None,
-            x_ref.data_ptr() if x_ref is not None else None, stream(),
-        ),
-        "pxa_pgd_tv2d_step",
-    )
-    if ev is not None:
-        _TIMER.end(ev)
+    _launch(lib.pxa_pgd_tv2d_step, dtcode(x), *pre, float(a), float(tau), int(prox), float(prox_w),
+            x.data_ptr(), x_prev.data_ptr(), hty.data_ptr(), x_new.data_ptr(), _p(partials), _p(x_ref), stream())
     return x_new
 
 
@@ -1489,55 +1536,39 @@ class PgdPlan:
                                     f64_array(k0), len(o1), i32_array(o1), f64_array(k1), float(h0), float(h1),
                                     float(lam), float(mu), int(prox), ct.byref(h)), "pxa_pgd_tv2d_plan")
         self._h = h.value
-        self._fn = lib.pxa_pgd_tv2d_plan_step
-        self._fn_fold = lib.pxa_pgd_tv2d_plan_step_fold
         self._free = lib.pxa_pgd_tv2d_plan_free
+
+    def _step(self, fn, x, x_prev, hty, x_new, a, tau, prox_w, *tail):
+        """One of the pxa_pgd_tv2d_plan_step* forms: each takes the plan, the three scalars and the four arrays, then
+        its own `tail` of partials / publication arguments, then the stream."""
+        _launch(fn, self._h, float(a), float(tau), float(prox_w), x.data_ptr(), x_prev.data_ptr(),
+                hty.data_ptr(), x_new.data_ptr(), *tail, stream())
+        return x_new
 
     def step(self, x, x_prev, hty, x_new, a, tau, prox_w, partials=None, x_ref=None, sink=None, seq=0,
              fold_launch=False):
         """One iteration; with `sink` (a HostFlagBuffer of (2, rows) values) its partials are also folded there
         under publication `seq`: by the launch's last workgroup, or with `fold_launch` by a fold launch enqueued
         behind it in the same C call (pxa_pgd_tv2d_plan_step_fold)."""
-        ev = _TIMER.begin() if _TIMER is not None else None  # measurement hook (bench.py), normally None
-        r = (self._fn_fold if fold_launch else self._fn)(self._h, float(a), float(tau), float(prox_w), x.data_ptr(), x_prev.data_ptr(), hty.data_ptr(),
-                     x_new.data_ptr(), partials.data_ptr() if partials is not None else None,
-                     x_ref.data_ptr() if x_ref is not None else None, sink.vptr if sink is not None else None,
-                     sink.fptr if sink is not None else None, int(seq), stream())
-        if r:
-            check(r, "pxa_pgd_tv2d_plan_step")
-        if ev is not None:
-            _TIMER.end(ev)
-        return x_new
+        vp_, fp_ = (None, None) if sink is None else (sink.vptr, sink.fptr)
+        fn = lib.pxa_pgd_tv2d_plan_step_fold if fold_launch else lib.pxa_pgd_tv2d_plan_step
+        return self._step(fn, x, x_prev, hty, x_new, a, tau, prox_w, _p(partials), _p(x_ref), vp_, fp_, int(seq))
 
     def step_wpub(self, x, x_prev, hty, x_new, a, tau, prox_w, partials, prev=None):
         """One iteration with window partials into `partials`; `prev` = (partials of the previous such launch,
         HostFlagBuffer, seq): folded and published by an extra workgroup of this launch
         (pxa_pgd_tv2d_plan_step_wpub)."""
-        ev = _TIMER.begin() if _TIMER is not None else None
         pp, fb, seq = prev if prev is not None else (None, None, 0)
-        r = lib.pxa_pgd_tv2d_plan_step_wpub(self._h, float(a), float(tau), float(prox_w), x.data_ptr(), x_prev.data_ptr(),
-                                            hty.data_ptr(), x_new.data_ptr(), partials.data_ptr(),
-                                            pp.data_ptr() if pp is not None else None, fb.vptr if fb is not None else None,
-                                            fb.fptr if fb is not None else None, int(seq), stream())
-        if r:
-            check(r, "pxa_pgd_tv2d_plan_step_wpub")
-        if ev is not None:
-            _TIMER.end(ev)
-        return x_new
+        vp_, fp_ = (None, None) if fb is None else (fb.vptr, fb.fptr)
+        return self._step(lib.pxa_pgd_tv2d_plan_step_wpub, x, x_prev, hty, x_new, a, tau, prox_w, partials.data_ptr(),
+                          _p(pp), vp_, fp_, int(seq))
 
     def step_window(self, x, x_prev, hty, x_new, a, tau, prox_w, partials, sink, seq):
         """One iteration whose partials are the RelError statistics of the (x, x_prev) pair it reads -- the stop
         check before it -- folded into `sink` under publication `seq` by a fold launch behind it
         (pxa_pgd_tv2d_plan_step_wfold)."""
-        ev = _TIMER.begin() if _TIMER is not None else None
-        r = lib.pxa_pgd_tv2d_plan_step_wfold(self._h, float(a), float(tau), float(prox_w), x.data_ptr(), x_prev.data_ptr(),
-                                             hty.data_ptr(), x_new.data_ptr(), partials.data_ptr(), sink.vptr, sink.fptr,
-                                             int(seq), stream())
-        if r:
-            check(r, "pxa_pgd_tv2d_plan_step_wfold")
-        if ev is not None:
-            _TIMER.end(ev)
-        return x_new
+        return self._step(lib.pxa_pgd_tv2d_plan_step_wfold, x, x_prev, hty, x_new, a, tau, prox_w, partials.data_ptr(),
+                          sink.vptr, sink.fptr, int(seq))
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -1545,7 +1576,7 @@ class PgdPlan:
             self._h = None
 
 
-_PDS_W = 17  # per-axis tap slots of pxa_pds_step (2 * 8 + 1)
+_PDS_W = 17  # PXA_PDS_TAP_SLOTS: per-axis tap slots of pxa_pds_step (2 * 8 + 1)
 
 
 def pds_args(stack, y_images, n0, n1, n2, D, taps, c0, c1, tau, sigma, rho, lam, prox, prox_w, h_kind):
@@ -1561,46 +1592,25 @@ def pds_args(stack, y_images, n0, n1, n2, D, taps, c0, c1, tau, sigma, rho, lam,
 
 def pds_step(algo, pre, x, u, z, hty, x_out, u_out, z_out, work_q, work_w, nseg=0):
     """One fused PD3O (algo 0) / Condat-Vu (algo 1) iteration (pxa_pds_step); `pre` from pds_args."""
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    ev = _TIMER.begin() if _TIMER is not None else None
-    check(lib.pxa_pds_step(dtcode(z), int(algo), *pre, p(x), p(u), p(z), p(hty), p(x_out), p(u_out), p(z_out),
-                           p(work_q), p(work_w), int(nseg), stream()), "pxa_pds_step")
-    if ev is not None:
-        _TIMER.end(ev)
+    _launch(lib.pxa_pds_step, dtcode(z), int(algo), *pre, _p(x), _p(u), _p(z), _p(hty), _p(x_out),
+            _p(u_out), _p(z_out), _p(work_q), _p(work_w), int(nseg), stream())
 
 
 def pds_step_la(algo, pre, primed, x, u, z, hty, x_out, u_out, z_out, work_q, work_kt, work_w, nseg=0):
     """One look-ahead PD3O / Condat-Vu iteration (pxa_pds_step_la): kernel B + kernel D (dual update fused
     with the next iteration's axis-0 march); `primed` = the previous call left x / work_q / work_kt."""
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    ev = _TIMER.begin() if _TIMER is not None else None
-    check(lib.pxa_pds_step_la(dtcode(z), int(algo), *pre, int(bool(primed)), p(x), p(u), p(z), p(hty), p(x_out),
-                              p(u_out), p(z_out), p(work_q), p(work_kt), p(work_w), int(nseg), stream()),
-          "pxa_pds_step_la")
-    if ev is not None:
-        _TIMER.end(ev)
+    _launch(lib.pxa_pds_step_la, dtcode(z), int(algo), *pre, int(bool(primed)), _p(x), _p(u), _p(z),
+            _p(hty), _p(x_out), _p(u_out), _p(z_out), _p(work_q), _p(work_kt), _p(work_w), int(nseg), stream())
 
 
-def _slab_operand(t, name, like, numel=None):
-    """A state or ghost array of the slab step: device tensor of `like`'s dtype, contiguous (never copied: the kernels
-    write into / read from exactly this buffer), optionally of `numel` elements."""
-    if t is None:
-        return None
-    if not (hasattr(t, "is_cuda") and t.is_cuda):
-        raise TypeError(f"pyxu_amd: `{name}` must be an MI355X device tensor")
-    if t.dtype != like.dtype:
-        raise TypeError(f"pyxu_amd: `{name}` has dtype {t.dtype}, the state has {like.dtype}")
-    if not t.is_contiguous():
-        raise ValueError(f"pyxu_amd: `{name}` must be contiguous")
-    if numel is not None and t.numel() != numel:
-        raise ValueError(f"pyxu_amd: `{name}` holds {t.numel()} elements, the slab geometry needs {numel}")
-    return t
+_SLAB = "the slab geometry"
 
 
 def _ghost_depth(t, name, like, per_plane):
     """Depth in planes of a ghost buffer whose planes hold `per_plane` elements each (0 for None)."""
-    if _slab_operand(t, name, like) is None:
+    if t is None:
         return 0
+    written(t, name, like=like, ctx=_SLAB)  # (read only, but never copied: the exchange fills exactly this buffer)
     d, rem = divmod(t.numel(), per_plane)
     if rem or d < 1:
         raise ValueError(f"pyxu_amd: ghost `{name}` of {t.numel()} elements is not a whole number of planes "
@@ -1616,10 +1626,12 @@ def pds_slab_primal(algo, pre, x, u, z, hty, x_out, u_out, work_q, work_w, src_l
     depth, n1, n2) for PD3O's z; None = the volume's edge.  Writes x_out, u_out (PD3O) and work_w."""
     stack, y_images, n0, n1, n2, D = (int(v) for v in pre[0])
     Mp, N = n1 * n2, n0 * n1 * n2
-    z = _slab_operand(z, "z", z, stack * D * N)
-    _slab_operand(hty, "hty", z, y_images * N)
-    for name, t in (("x", x), ("u", u), ("x_out", x_out), ("u_out", u_out), ("work_q", work_q), ("work_w", work_w)):
-        _slab_operand(t, name, z, stack * N)
+    # state arrays as they are, inputs too: the kernels read from / write into exactly these buffers
+    written(z, "z", numel=stack * D * N, ctx=_SLAB)
+    for name, t, numel in (("hty", hty, y_images * N), ("x", x, stack * N), ("u", u, stack * N), ("x_out", x_out, stack * N),
+                           ("u_out", u_out, stack * N), ("work_q", work_q, stack * N), ("work_w", work_w, stack * N)):
+        if t is not None:
+            written(t, name, like=z, numel=numel, ctx=_SLAB)
     zdirs = D if algo == 0 else 1
     depths = [_ghost_depth(src_lo, "src_lo", z, stack * Mp), _ghost_depth(src_hi, "src_hi", z, stack * Mp),
               _ghost_depth(z_lo, "z_lo", z, stack * zdirs * Mp), _ghost_depth(z_hi, "z_hi", z, stack * zdirs * Mp)]
@@ -1629,13 +1641,8 @@ def pds_slab_primal(algo, pre, x, u, z, hty, x_out, u_out, work_q, work_w, src_l
             raise ValueError(f"pyxu_amd: ghost `{name}` aliases an output of the step")
     if algo == 1 and x_out is not None and x is not None and x_out.data_ptr() == x.data_ptr():
         raise ValueError("pyxu_amd: Condat-Vu's x_out must not alias x")
-    p = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-    ev = _TIMER.begin() if _TIMER is not None else None
-    check(lib.pxa_pds_slab_primal(dtcode(z), int(algo), *pre, p(x), p(u), p(z), p(hty), p(x_out), p(u_out), p(work_q),
-                                  p(work_w), i64_array(depths), p(src_lo), p(src_hi), p(z_lo), p(z_hi), int(nseg),
-                                  stream()), "pxa_pds_slab_primal")
-    if ev is not None:
-        _TIMER.end(ev)
+    _launch(lib.pxa_pds_slab_primal, dtcode(z), int(algo), *pre, _p(x), _p(u), _p(z), _p(hty), _p(x_out), _p(u_out),
+            _p(work_q), _p(work_w), i64_array(depths), _p(src_lo), _p(src_hi), _p(z_lo), _p(z_hi), int(nseg), stream())
 
 
 def pds_slab_dual(w, z, geom, c0, c1, sigma, lam, rho, h_kind, relax=0, w_hi=None, out=None):
@@ -1644,20 +1651,13 @@ def pds_slab_dual(w, z, geom, c0, c1, sigma, lam, rho, h_kind, relax=0, w_hi=Non
     slab's w as (stack, depth, n1, n2), None at the volume's last slab.  geom = (stack, nl, n1, n2, D)."""
     stack, n0, n1, n2, D = (int(v) for v in geom)
     N = n0 * n1 * n2
-    z = _slab_operand(z, "z", z, stack * D * N)
-    _slab_operand(w, "w", z, stack * N)
+    written(z, "z", numel=stack * D * N, ctx=_SLAB)
+    written(w, "w", like=z, numel=stack * N, ctx=_SLAB)
     depth = _ghost_depth(w_hi, "w_hi", z, stack * n1 * n2)
-    out = empty_like(z) if out is None else _slab_operand(out, "out", z, z.numel())
-    for name, t in (("w", w), ("w_hi", w_hi)):
-        if t is not None and t.data_ptr() == out.data_ptr():
-            raise ValueError(f"pyxu_amd: `{name}` aliases the output of the dual update")
-    ev = _TIMER.begin() if _TIMER is not None else None
-    check(lib.pxa_pds_slab_dual(dtcode(z), int(relax), i64_array([stack, n0, n1, n2, D]),
-                                f64_array(list(c0) + list(c1)), float(sigma), float(lam), float(rho), int(h_kind),
-                                ptr(w), None if w_hi is None else ptr(w_hi), depth, ptr(z), ptr(out), stream()),
-          "pxa_pds_slab_dual")
-    if ev is not None:
-        _TIMER.end(ev)
+    out = _out(out, z, apart=(w, w_hi))
+    _launch(lib.pxa_pds_slab_dual, dtcode(z), int(relax), i64_array([stack, n0, n1, n2, D]),
+            f64_array(list(c0) + list(c1)), float(sigma), float(lam), float(rho), int(h_kind), ptr(w), _p(w_hi), depth,
+            ptr(z), ptr(out), stream())
     return out
 
 
@@ -1672,7 +1672,7 @@ def tv_dual_update(w, z, geom, c0, c1, sigma, lam, rho, h_kind, relax=0, out=Non
     if w.numel() != stack * n0 * n1 * n2 or z.numel() != D * w.numel():
         raise ValueError(f"pyxu_amd: tv_dual_update geometry {tuple(geom)} does not match w {tuple(w.shape)}, "
                          f"z {tuple(z.shape)}")
-    out = empty_like(z) if out is None else require(out, "out")
+    out = _out(out, z, apart=(w,))
     check(lib.pxa_tv_dual_update(dtcode(z), int(relax), i64_array([stack, n0, n1, n2, D]),
                                  f64_array(list(c0) + list(c1)), float(sigma), float(lam), float(rho), int(h_kind),
                                  ptr(w), ptr(z), ptr(out), stream()), "pxa_tv_dual_update")
@@ -1693,16 +1693,12 @@ def fft(z, shape, axes, stack, inverse, out=None):
     """Unnormalised DFT over `axes` of `stack` complex arrays of `shape`, interleaved (re, im) real
     tensors (pxa_fft).  inverse=False: exp(-2 pi i ..) (fftn, norm="backward"); True: exp(+..)
     (ifftn, norm="forward")."""
-    torch = _torch()
     z = require(z, "z")
-    out = empty_like(z) if out is None else out
+    out = _out(out, z)  # (may be z)
     sh, ax = i64_array(shape), int_array(axes)
-    wsz = int(lib.pxa_fft_workspace_bytes(dtcode(z), len(shape), sh, len(axes), ax, int(stack)))
-    if wsz == (1 << 64) - 1:  # (size_t)-1: arguments outside the envelope
-        check(-3, "pxa_fft_workspace_bytes")  # PXA_ERR_UNSUPPORTED
-    work = torch.empty((wsz,), dtype=torch.uint8, device=z.device) if wsz > 0 else None
+    work = _workspace("pxa_fft_workspace_bytes", z, dtcode(z), len(shape), sh, len(axes), ax, int(stack))
     check(lib.pxa_fft_ex(dtcode(z), len(shape), sh, len(axes), ax, int(stack), int(bool(inverse)), ptr(z), ptr(out),
-                         ptr(work) if work is not None else None, stream()), "pxa_fft_ex")
+                         _p(work), stream()), "pxa_fft_ex")
     return out
 
 
@@ -1723,7 +1719,7 @@ def complex_real_part(z):
 def complex_mul(a, b, conj_b=False, out=None):
     """out = a * b (b broadcast over a's leading stack) for interleaved complex tensors."""
     a, b = require(a, "a"), require(b, "b")
-    out = empty_like(a) if out is None else out
+    out = _out(out, a)
     check(lib.pxa_complex_mul(dtcode(a), a.numel() // 2, b.numel() // 2, ptr(a), ptr(b), int(bool(conj_b)), ptr(out),
                               stream()), "pxa_complex_mul")
     return out
@@ -1739,30 +1735,24 @@ def nudft_tiles(dtype_code):
 
 def nudft_splits(dtype_code, D, Q, M, N, splits=0):
     """Source splits pxa_nudft runs with for these shapes (`splits` = 0: the library's choice)."""
-    wsz = int(lib.pxa_nudft_workspace_bytes(int(dtype_code), int(D), int(Q), int(M), int(N), int(splits)))
-    if wsz == (1 << 64) - 1:
-        check(-3, "pxa_nudft_workspace_bytes")  # PXA_ERR_UNSUPPORTED
+    wsz = _workspace_bytes("pxa_nudft_workspace_bytes", int(dtype_code), int(D), int(Q), int(M), int(N), int(splits))
     return 1 if wsz == 0 else wsz // (Q * N * 2 * (4 if dtype_code == 0 else 8))
 
 
 def nudft(src, tgt, isign, w, splits=0, out=None):
     """out[q, n] = sum_m w[q, m] exp(i isign <src_m, tgt_n>) (pxa_nudft): src (M, D), tgt (N, D), w (Q, 2 M) and
     out (Q, 2 N) interleaved complex."""
-    torch = _torch()
     src, tgt, w = require(src, "src"), require(tgt, "tgt"), require(w, "w")
     if not (src.dtype == tgt.dtype == w.dtype):
         raise TypeError("pyxu_amd: nudft operands must share one dtype.")
     (M, D), N, Q = src.shape, tgt.shape[0], w.shape[0]
     if tgt.shape[1] != D or w.shape[1] != 2 * M:
         raise ValueError(f"nudft: src {tuple(src.shape)}, tgt {tuple(tgt.shape)}, w {tuple(w.shape)} do not match.")
-    out = empty((Q, 2 * N), w) if out is None else out
+    out = _out(out, w, (Q, 2 * N), apart=(src, tgt, w))
     dt = dtcode(w)
-    wsz = int(lib.pxa_nudft_workspace_bytes(dt, D, Q, M, N, int(splits)))
-    if wsz == (1 << 64) - 1:
-        check(-3, "pxa_nudft_workspace_bytes")  # PXA_ERR_UNSUPPORTED
-    work = torch.empty((wsz,), dtype=torch.uint8, device=w.device) if wsz > 0 else None
-    check(lib.pxa_nudft(dt, D, Q, M, N, ptr(src), ptr(tgt), int(isign), ptr(w), ptr(out), int(splits),
-                        ptr(work) if work is not None else None, stream()), "pxa_nudft")
+    work = _workspace("pxa_nudft_workspace_bytes", w, dt, D, Q, M, N, int(splits))
+    check(lib.pxa_nudft(dt, D, Q, M, N, ptr(src), ptr(tgt), int(isign), ptr(w), ptr(out), int(splits), _p(work), stream()),
+          "pxa_nudft")
     return out
 
 
@@ -1788,11 +1778,14 @@ def _nufft_plan_check(plan, name):
     return M, D
 
 
-def _nufft_fac_check(fac, M, like, name):
-    fac = require(fac, "fac")
-    if fac.numel() != 2 * M or fac.dtype != like.dtype:
-        raise ValueError(f"{name}: fac {tuple(fac.shape)} {fac.dtype} does not match {M} points of {like.dtype}.")
-    return fac
+def _nufft_call(name, args, fac, conj, M, like, out):
+    """lib.<name>(*args, stream), or with `fac` (2 M interleaved complex of like's dtype) its `_fac` form, which takes
+    the factors and the conjugation flag behind them."""
+    if fac is not None:
+        fac = require(fac, "fac", like=like, numel=2 * M)
+        name, args = name + "_fac", args + [ptr(fac), int(bool(conj))]
+    check(getattr(lib, name)(*args, stream()), name)
+    return out
 
 
 def nufft_spread(nf, w, beta, plan, c, out=None, fac=None, conj=False):
@@ -1808,16 +1801,10 @@ def nufft_spread(nf, w, beta, plan, c, out=None, fac=None, conj=False):
     nbins = int(np.prod([-(-int(f) // e) for f, e in zip(nf, nufft_grid_tiles(dtcode(c), D)[0])]))
     if bin_start.numel() != nbins + 1:
         raise ValueError(f"nufft_spread: bin_start has {bin_start.numel()} entries, the grid {nbins} bins.")
-    out = empty((Q, 2 * int(np.prod(nf))), c) if out is None else out
-    if fac is not None:
-        fac = _nufft_fac_check(fac, M, c, "nufft_spread")
-        check(lib.pxa_nufft_spread_fac(dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
-                                       ptr(perm), ptr(bin_start), ptr(c), ptr(out), ptr(fac), int(bool(conj)),
-                                       stream()), "pxa_nufft_spread_fac")
-        return out
-    check(lib.pxa_nufft_spread(dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off), ptr(perm),
-                               ptr(bin_start), ptr(c), ptr(out), stream()), "pxa_nufft_spread")
-    return out
+    out = _out(out, c, (Q, 2 * int(np.prod(nf))), apart=(c,))
+    args = [dtcode(c), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off), ptr(perm), ptr(bin_start), ptr(c),
+            ptr(out)]
+    return _nufft_call("pxa_nufft_spread", args, fac, conj, M, c, out)
 
 
 def nufft_interp(nf, w, beta, plan, grid, out=None, fac=None, conj=False):
@@ -1830,16 +1817,9 @@ def nufft_interp(nf, w, beta, plan, grid, out=None, fac=None, conj=False):
     Q = grid.shape[0]
     if len(nf) != D or grid.shape[1] != 2 * int(np.prod(nf)) or off.dtype != grid.dtype:
         raise ValueError(f"nufft_interp: nf {tuple(nf)}, off {tuple(off.shape)}, grid {tuple(grid.shape)} do not match.")
-    out = empty((Q, 2 * M), grid) if out is None else out
-    if fac is not None:
-        fac = _nufft_fac_check(fac, M, grid, "nufft_interp")
-        check(lib.pxa_nufft_interp_fac(dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
-                                       ptr(perm), ptr(grid), ptr(out), ptr(fac), int(bool(conj)), stream()),
-              "pxa_nufft_interp_fac")
-        return out
-    check(lib.pxa_nufft_interp(dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off),
-                               ptr(perm), ptr(grid), ptr(out), stream()), "pxa_nufft_interp")
-    return out
+    out = _out(out, grid, (Q, 2 * M), apart=(grid,))
+    args = [dtcode(grid), D, Q, M, i64_array(nf), int(w), float(beta), ptr(l0), ptr(off), ptr(perm), ptr(grid), ptr(out)]
+    return _nufft_call("pxa_nufft_interp", args, fac, conj, M, grid, out)
 
 
 def nufft_deconv(N, nf, modeord, to_grid, corr, z, out=None):
@@ -1850,7 +1830,7 @@ def nufft_deconv(N, nf, modeord, to_grid, corr, z, out=None):
     if len(N) != len(nf) or z.shape[1] != 2 * n_in or corr.numel() != sum(N) or corr.dtype != z.dtype:
         raise ValueError(f"nufft_deconv: N {tuple(N)}, nf {tuple(nf)}, z {tuple(z.shape)}, corr {tuple(corr.shape)} "
                          "do not match.")
-    out = empty((Q, 2 * n_out), z) if out is None else out
+    out = _out(out, z, (Q, 2 * n_out), apart=(z, corr))
     check(lib.pxa_nufft_deconv(dtcode(z), len(N), Q, i64_array(N), i64_array(nf), int(modeord), int(bool(to_grid)),
                                ptr(corr), ptr(z), ptr(out), stream()), "pxa_nufft_deconv")
     return out
@@ -1860,30 +1840,24 @@ def nufft_deconv(N, nf, modeord, to_grid, corr, z, out=None):
 def toeplitz_workspace_bytes(dtype_code, Q, n, p):
     """Workspace of pxa_toeplitz_apply in bytes, or None for lengths outside the fused kernel's envelope (a `p`
     that is not {2, 3, 5, 7}-smooth, not LDS-resident or below 2 n - 1).  Needs no GPU."""
-    wsz = int(lib.pxa_toeplitz_workspace_bytes(int(dtype_code), len(n), int(Q), i64_array(n), i64_array(p)))
-    return None if wsz == (1 << 64) - 1 else wsz
+    return _workspace_bytes("pxa_toeplitz_workspace_bytes", int(dtype_code), len(n), int(Q), i64_array(n), i64_array(p),
+                            unsupported_ok=True)
 
 
 def toeplitz_apply(n, p, split, khat, z, out=None):
     """out (Q, 2 prod n) = crop(ifft(khat . fft(pad(z)))) on the cells p (pxa_toeplitz_apply): the circular
     convolution with the real spectrum `khat` (prod p values, every scaling folded in); sample i of axis d sits in
     cell i (i < split[d]) or i + p[d] - n[d].  `out` may be `z`."""
-    torch = _torch()
     z, khat = require(z, "z"), require(khat, "khat")
     Q, cells = z.shape[0], int(np.prod(n))
     if not (len(n) == len(p) == len(split)) or z.shape[1] != 2 * cells or khat.numel() != int(np.prod(p)) \
             or khat.dtype != z.dtype:
         raise ValueError(f"toeplitz_apply: n {tuple(n)}, p {tuple(p)}, split {tuple(split)}, z {tuple(z.shape)}, khat "
                          f"{tuple(khat.shape)} do not match.")
-    out = empty((Q, 2 * cells), z) if out is None else out
-    if tuple(out.shape) != (Q, 2 * cells) or out.dtype != z.dtype or not out.is_contiguous():
-        raise ValueError(f"toeplitz_apply: out {tuple(out.shape)} {out.dtype} does not match z {tuple(z.shape)}.")
-    wsz = toeplitz_workspace_bytes(dtcode(z), Q, n, p)
-    if wsz is None:
-        check(-3, "pxa_toeplitz_workspace_bytes")  # PXA_ERR_UNSUPPORTED
-    work = torch.empty((wsz,), dtype=torch.uint8, device=z.device) if wsz > 0 else None
+    out = _out(out, z, apart=(khat,))  # (may be z)
+    work = _workspace("pxa_toeplitz_workspace_bytes", z, dtcode(z), len(n), Q, i64_array(n), i64_array(p))
     check(lib.pxa_toeplitz_apply(dtcode(z), len(n), Q, i64_array(n), i64_array(p), i64_array(split), ptr(khat), ptr(z),
-                                 ptr(out), ptr(work) if work is not None else None, stream()), "pxa_toeplitz_apply")
+                                 ptr(out), _p(work), stream()), "pxa_toeplitz_apply")
     return out
 
 

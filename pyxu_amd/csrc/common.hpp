@@ -150,7 +150,7 @@ __device__ inline double fold_tile_stat(const double* __restrict__ pr, int64_t p
 // workgroups of kBlock threads, block b owning elements [b chunk, (b + 1) chunk), chunk = ceil(n / blocks),
 // thread t summing elements lo + t, lo + t + kBlock, ... in order, then cg_block_sum.  Shared by cg.hip and
 // the dense normal operator's fused reduction (dense.hip), so that both give the same bits.
-constexpr int kCgBlocks = 64;
+constexpr int kCgBlocks = PXA_CG_BLOCKS;
 inline int cg_blocks(int64_t n) { return (int)(n < (int64_t)kCgBlocks * kBlock ? (n + kBlock - 1) / kBlock : kCgBlocks); }
 
 // shuffle-down fold per wavefront, then thread 0 adds the kBlock / 64 wave results in order (valid in thread

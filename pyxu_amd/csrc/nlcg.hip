@@ -31,7 +31,7 @@ __device__ inline double fold(const double* __restrict__ part, int64_t row, int 
   return s;
 }
 
-constexpr int kVarFR = 0, kVarPR = 1;
+constexpr int kVarFR = PXA_NLCG_FR, kVarPR = PXA_NLCG_PR;
 
 template <typename T, int VAR>
 __global__ void __launch_bounds__(kBlock) nlcg_dot_kernel(int64_t n, const T* __restrict__ g1, const T* __restrict__ g0,

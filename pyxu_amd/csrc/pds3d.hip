@@ -681,11 +681,12 @@ int pds_setup(int algo, const int64_t* geom, const int32_t* ntaps, const int32_t
   PXA_CHECK_ARG(algo == 0 || algo == 1);
   PXA_CHECK_ARG(geom && ntaps && offs && coefs && scal);
   if (const int e = make_geom<T>(geom[0], geom[1], geom[2], geom[3], geom[4], geom[5], diff, S.g)) return e;
+  static_assert(PXA_PDS_TAP_SLOTS == 2 * kMaxR + 1, "the tap slots hold one dense window of reach kMaxR");
   PXA_CHECK_ARG(prox >= 0 && prox <= 2 && (h_kind == 0 || h_kind == 1));
-  for (int a = 0; a < 3; ++a) PXA_CHECK_ARG(ntaps[a] >= 1 && ntaps[a] <= 2 * kMaxR + 1);
+  for (int a = 0; a < 3; ++a) PXA_CHECK_ARG(ntaps[a] >= 1 && ntaps[a] <= PXA_PDS_TAP_SLOTS);
   int Ra[3];
   for (int a = 0; a < 3; ++a) {
-    Ra[a] = tap_window(ntaps[a], offs + a * (2 * kMaxR + 1), coefs + a * (2 * kMaxR + 1), S.kw[a]);
+    Ra[a] = tap_window(ntaps[a], offs + a * PXA_PDS_TAP_SLOTS, coefs + a * PXA_PDS_TAP_SLOTS, S.kw[a]);
     if (Ra[a] < 0) return PXA_ERR_UNSUPPORTED;
   }
   // axis 0 is the identity iff its window is exactly [1] at offset 0

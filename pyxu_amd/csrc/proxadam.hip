@@ -20,8 +20,8 @@
 namespace pxa {
 namespace {
 
-constexpr int kAdam = 0, kAmsgrad = 1, kPadam = 2;
-constexpr int kProxL1 = 1, kProxPos = 2, kProxPosL1 = 3, kProxBox = 4;
+constexpr int kAdam = PXA_PROXADAM_ADAM, kAmsgrad = PXA_PROXADAM_AMSGRAD, kPadam = PXA_PROXADAM_PADAM;
+constexpr int kProxL1 = PXA_PROX_L1, kProxPos = PXA_PROX_POS, kProxPosL1 = PXA_PROX_POSL1, kProxBox = PXA_PROX_BOX;
 
 template <typename T>
 inline int64_t pa_chunk(int64_t n, int nb) {
@@ -310,7 +310,7 @@ int launch_sub(int kind, int k, int64_t rows, int64_t n, double mom, double eps,
   double* parts = (double*)work + rows * nb;
   const double* part_prev = parts + (size_t)((k - 1) & 1) * 2 * rows * nb;
   double* part_cur = parts + (size_t)(k & 1) * 2 * rows * nb;
-  const double* psimax = (double*)work + 5 * rows * nb;
+  const double* psimax = (double*)work + PXA_PROXADAM_PLANES * rows * nb;
   int32_t* state = (int32_t*)(psimax + rows);
   int32_t* counters = state + rows;
   const dim3 grid((unsigned)nb, (unsigned)rows);
@@ -353,7 +353,7 @@ int pxa_proxadam_blocks(int64_t rows, int64_t n) { return rows > 0 && n > 0 ? bl
 size_t pxa_proxadam_workspace_bytes(int64_t rows, int64_t n) {
   if (rows <= 0 || n <= 0) return 0;
   const size_t nb = (size_t)blocks_per_row(rows, n), r = (size_t)rows;
-  return (5 * r * nb + r) * sizeof(double) + (r + 2 + (r & 1)) * sizeof(int32_t);
+  return (PXA_PROXADAM_PLANES * r * nb + r) * sizeof(double) + (r + 2 + (r & 1)) * sizeof(int32_t);
 }
 
 int pxa_proxadam_moments(int dtype, int variant, int first, int64_t rows, int64_t n, double b1, double omb1, double b2,
@@ -376,7 +376,7 @@ int pxa_proxadam_sub_init(int64_t rows, int64_t n, void* work, void* stream) {
   PXA_CHECK_ARG(rows >= 1 && rows <= 65535 && n >= 1 && work);
   const int nb = blocks_per_row(rows, n);
   double* part_max = (double*)work;
-  double* psimax = part_max + 5 * rows * nb;
+  double* psimax = part_max + PXA_PROXADAM_PLANES * rows * nb;
   int32_t* state = (int32_t*)(psimax + rows);
   int32_t* counters = state + rows;
   const int per = kBlock / kWave;

@@ -19,7 +19,7 @@
 namespace pxa {
 namespace {
 
-constexpr int kNone = 0, kProxL1 = 1, kProxPos = 2, kProxPosL1 = 3, kProxBox = 4;  // _dev.PROX_*
+constexpr int kNone = 0, kProxL1 = PXA_PROX_L1, kProxPos = PXA_PROX_POS, kProxPosL1 = PXA_PROX_POSL1, kProxBox = PXA_PROX_BOX;
 
 struct Words {
   uint32_t w[4];
